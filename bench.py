@@ -1,8 +1,13 @@
 #!/usr/bin/env python
 """bench.py -- Llama-3-8B GGUF Q4_K_M, 512-token prefill / 256-token greedy decode on MI355X (BASELINE.json configs[1]).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run builds the model, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`, prompt TTFT, step roofline fraction);
+`--dump-outputs DIR` also writes what the last timed step computed (dump_outputs()).  `--full` adds every side measurement after the headline: the bf16
+prompt path, the live roofline of the dominant kernel, all-reduce costs, the drop-in launch sequence, the CPU baseline + parity legs, batched decode and
+the extra BASELINE configurations.
 
 A "step" is ONE decode step (one new token through embedding -> 32 blocks -> norm -> lm_head -> greedy sample) at
 batch 1, replayed from a HIP graph; the timed region is exactly K steps after W warm-up steps, bracketed by
@@ -574,6 +579,81 @@ def extra_config(kind, dev, steps=64, warmup=4, prompt_len=512):
     return out
 
 
+def gate_up_roofline(model, cfg, dev, model_name, quant):
+    """`roofline` of the line (--full): the dominant kernel, the decode engine's gate/up phase (RMSNorm + Q8_K quantize + 2 x [ffn, d] GEMV + SiLU*up), timed with HIP
+    events on the launch stream over every layer's weights (>= 1 GB: nothing Infinity-Cache resident).  `frac` is what THIS process measured; the in-graph average of the
+    committed rocprofv3 trace (launch boundary included) is the side object `in_graph`, quoted only when the profile was taken from this very build (source digest)."""
+    import ctypes as C
+    import torch
+    from mistralrs_amd import _lib
+    ext = _lib.load("ext")
+
+    class Mat(C.Structure):
+        _fields_ = [("planes", C.c_void_p), ("type", C.c_int), ("n", C.c_longlong), ("k", C.c_longlong)]
+    MP = C.POINTER(Mat)
+    ext.mrs_dec_gate_up.argtypes = [MP, MP, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    h = torch.randn(1, cfg.hidden_size, device=dev)
+    act = torch.empty(1, cfg.intermediate_size, device=dev)
+    st = torch.cuda.current_stream().cuda_stream
+    assert model.decode_path == "engine", model.decode_path
+    layers = []
+    moe = cfg.num_experts > 0
+    sfx = "_exps" if moe else ""
+    for i in range(cfg.num_layers):
+        g, u = model._keep[f"blk.{i}.ffn_gate{sfx}.weight"], model._keep[f"blk.{i}.ffn_up{sfx}.weight"]
+        layers.append((Mat(model._keep[f"blk.{i}.ffn_gate{sfx}.weight#dec"].data_ptr(), g.dtype.id, g.shape[0], g.shape[1]),
+                       Mat(model._keep[f"blk.{i}.ffn_up{sfx}.weight#dec"].data_ptr(), u.dtype.id, u.shape[0], u.shape[1]),
+                       model._keep[f"blk.{i}.ffn_norm.weight"], (g.nbytes() + u.nbytes()) * (cfg.num_experts_per_tok / cfg.num_experts if moe else 1)))
+    if moe:  # the top-k experts' gate / up rows in ONE launch (mrs_dec_gate_up_topk); expert ids on the device
+        ext.mrs_dec_gate_up_topk.argtypes = [MP, MP, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        sel = torch.tensor([1, 5][: cfg.num_experts_per_tok], dtype=torch.int32, device=dev)
+        act = torch.empty(cfg.num_experts_per_tok, cfg.intermediate_size, device=dev)
+
+    def gate_up_pass():
+        for mg, mu, nw, _ in layers:
+            if moe:
+                rc = ext.mrs_dec_gate_up_topk(C.byref(mg), C.byref(mu), cfg.intermediate_size, sel.data_ptr(), cfg.num_experts_per_tok, h.data_ptr(), nw.data_ptr(), cfg.rms_eps, 0,
+                                              act.data_ptr(), cfg.intermediate_size, st)
+            else:
+                rc = ext.mrs_dec_gate_up(C.byref(mg), C.byref(mu), cfg.intermediate_size, None, h.data_ptr(), cfg.hidden_size, nw.data_ptr(), cfg.rms_eps, 0,
+                                         act.data_ptr(), cfg.intermediate_size, 1, st)
+            assert rc == 0
+    gate_up_pass()
+    torch.cuda.synchronize()
+    reps = 8
+    k0, k1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    k0.record()
+    for _ in range(reps):
+        gate_up_pass()
+    k1.record()
+    torch.cuda.synchronize()
+    kern_s = k0.elapsed_time(k1) / 1e3 / (reps * len(layers))
+    kern_bytes = int(layers[0][3])  # algorithmic bytes per launch: the two GGUF weight tensors (the decode layout holds the same bits + 2.8 % for 8-bit scales)
+    achieved = kern_bytes / kern_s
+    rl = {"bound": "hbm", "kernel": "dec_gemv_kernel<1, EPI_GLU> (decode engine gate/up phase: RMSNorm + Q8_K quantize + gate/up GEMV + SiLU*up)",
+          "achieved": round(achieved / 1e9, 1), "peak": HBM_PEAK / 1e9, "unit": "GB/s", "frac": round(achieved / HBM_PEAK, 4),
+          "bytes_per_launch": int(kern_bytes), "us_per_launch": round(kern_s * 1e6, 2),
+          "frac_source": "live: HIP events on the launch stream over back-to-back launches of every layer's weights, this process", "source_digest": source_digest(),
+          **committed_profile(model_name, quant)}
+    if rl.get("in_graph"):
+        rl["in_graph"]["achieved"] = round(kern_bytes / (rl["in_graph"]["us_per_launch"] * 1e-6) / 1e9, 1)
+        rl["in_graph"]["frac"] = round(kern_bytes / (rl["in_graph"]["us_per_launch"] * 1e-6) / HBM_PEAK, 4)
+    return rl
+
+
+def dump_outputs(model, r, warmup, steps, out_dir):
+    """--dump-outputs: what the timed decode path hands its caller, read back after the last timed step.  `logits` [B, vocab] f32 = the logits of that step (the lm_head
+    output every sequence of the batch sampled from), `next_tokens` [B] = the greedy ids it sampled, `tokens` [B, steps] = the ids of all timed steps (ids stored as
+    float64: exact).  Weights, prompt and step count depend on the arguments only, so two builds run with the same arguments can be compared array for array."""
+    import numpy as np
+    B = r["B"]
+    toks = model.tokens_out[:B, warmup: warmup + steps].cpu().numpy().astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "logits.npy"), model.logits[:B].float().cpu().numpy())
+    np.save(os.path.join(out_dir, "next_tokens.npy"), toks[:, -1].copy())
+    np.save(os.path.join(out_dir, "tokens.npy"), toks)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -596,7 +676,14 @@ def main():
     ap.add_argument("--parity-positions", type=int, default=16, help="greedy positions of the CPU-path parity leg")
     ap.add_argument("--quant", choices=["q4_k_m", "q8_0_isq"], default="q4_k_m",
                     help="q8_0_isq = BASELINE configs[2]: every linear quantized in situ from bf16 weights to Q8_0 on the GPU (mistralrs_amd.isq, role of generate_isq!)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements after the headline: bf16 prompt path, live roofline of the dominant kernel, all-reduce costs, drop-in launch "
+                         "sequence, CPU baseline + parity, batched decode, extra configurations (--no-cpu-baseline / --no-dropin / --no-extra skip single legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (logits, sampled tokens; see dump_outputs())")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # driver contract: `python bench.py --gpus N` must use N GPUs -- re-launch ourselves as one process per GPU (mistralrs-core/src/distributed.rs:569-795
@@ -713,9 +800,11 @@ def main():
             p2p, p2p_note = None, "rccl only (the p2p route raised its error word during the timed pass: dropped, pass repeated on RCCL)"
             r = timed_run(model, cfg, a.prompt_len, a.steps, a.warmup, a.batch, sync, world, dev)
     prompt, ttft, prefill_flops, B, t_all, dev_s, toks = r["prompt"], r["ttft"], r["prefill_flops"], r["B"], r["t_all"], r["dev_s"], r["toks"]
+    if a.dump_outputs and rank == 0:
+        dump_outputs(model, r, a.warmup, a.steps, a.dump_outputs)
     prefill_exact = bool(model.prefill_is_exact)
     ttft_bf16, ttft_bf16_fused = None, None
-    if prefill_exact and world == 1:  # the same prompt through the bf16-operand MFMA GEMMs + flash attention (selectable: Llama.set_prefill_mode(0) / MRS_PREFILL_EXACT=0)
+    if a.full and prefill_exact and world == 1:  # the same prompt through the bf16-operand MFMA GEMMs + flash attention (selectable: Llama.set_prefill_mode(0) / MRS_PREFILL_EXACT=0)
         def timed_prefill(mode):
             model.set_prefill_mode(mode)
             model.prefill(prompt, 0, seq=min(1, cfg.max_batch - 1))
@@ -728,58 +817,12 @@ def main():
             ttft_bf16_fused = timed_prefill(2)  # A / B: the fused block-dequant -> bf16 MFMA kernels of rounds 2-5 on the same prompt
         model.set_prefill_mode(-1)
 
-    # ---------------- roofline of the dominant kernel: the decode engine's gate/up phase (RMSNorm + Q8_K quantize + 2 x [ffn, d] GEMV + SiLU*up),
-    # timed with HIP events on the launch stream over every layer's weights (>= 1 GB: nothing Infinity-Cache resident)
-    import ctypes as C
-    from mistralrs_amd import _lib
-    ext = _lib.load("ext")
-
-    class Mat(C.Structure):
-        _fields_ = [("planes", C.c_void_p), ("type", C.c_int), ("n", C.c_longlong), ("k", C.c_longlong)]
-    MP = C.POINTER(Mat)
-    ext.mrs_dec_gate_up.argtypes = [MP, MP, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-    h = torch.randn(1, cfg.hidden_size, device=dev)
-    act = torch.empty(1, cfg.intermediate_size, device=dev)
-    st = torch.cuda.current_stream().cuda_stream
-    assert model.decode_path == "engine", model.decode_path
-    layers = []
     moe = cfg.num_experts > 0
-    sfx = "_exps" if moe else ""
-    for i in range(cfg.num_layers):
-        g, u = model._keep[f"blk.{i}.ffn_gate{sfx}.weight"], model._keep[f"blk.{i}.ffn_up{sfx}.weight"]
-        layers.append((Mat(model._keep[f"blk.{i}.ffn_gate{sfx}.weight#dec"].data_ptr(), g.dtype.id, g.shape[0], g.shape[1]),
-                       Mat(model._keep[f"blk.{i}.ffn_up{sfx}.weight#dec"].data_ptr(), u.dtype.id, u.shape[0], u.shape[1]),
-                       model._keep[f"blk.{i}.ffn_norm.weight"], (g.nbytes() + u.nbytes()) * (cfg.num_experts_per_tok / cfg.num_experts if moe else 1)))
-    if moe:  # the top-k experts' gate / up rows in ONE launch (mrs_dec_gate_up_topk); expert ids on the device
-        ext.mrs_dec_gate_up_topk.argtypes = [MP, MP, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
-        sel = torch.tensor([1, 5][: cfg.num_experts_per_tok], dtype=torch.int32, device=dev)
-        act = torch.empty(cfg.num_experts_per_tok, cfg.intermediate_size, device=dev)
-
-    def gate_up_pass():
-        for mg, mu, nw, _ in layers:
-            if moe:
-                rc = ext.mrs_dec_gate_up_topk(C.byref(mg), C.byref(mu), cfg.intermediate_size, sel.data_ptr(), cfg.num_experts_per_tok, h.data_ptr(), nw.data_ptr(), cfg.rms_eps, 0,
-                                              act.data_ptr(), cfg.intermediate_size, st)
-            else:
-                rc = ext.mrs_dec_gate_up(C.byref(mg), C.byref(mu), cfg.intermediate_size, None, h.data_ptr(), cfg.hidden_size, nw.data_ptr(), cfg.rms_eps, 0,
-                                         act.data_ptr(), cfg.intermediate_size, 1, st)
-            assert rc == 0
-    gate_up_pass()
-    torch.cuda.synchronize()
-    reps = 8
-    k0, k1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    k0.record()
-    for _ in range(reps):
-        gate_up_pass()
-    k1.record()
-    torch.cuda.synchronize()
-    kern_s = k0.elapsed_time(k1) / 1e3 / (reps * len(layers))
-    kern_bytes = int(layers[0][3])  # algorithmic bytes per launch: the two GGUF weight tensors (the decode layout holds the same bits + 2.8 % for 8-bit scales)
-    achieved = kern_bytes / kern_s
+    roofline = gate_up_roofline(model, cfg, dev, name, a.quant) if a.full else None
 
     # ---------------- tensor parallel: cost of the decode all-reduces (2 per layer, [1, hidden] f32) measured on the same communicator
     ar = None
-    if tp:
+    if tp and a.full:
         buf = torch.zeros(cfg.hidden_size, device=dev)
         for _ in range(10):
             comm.all_reduce_(buf)
@@ -824,20 +867,10 @@ def main():
                                      + "; whole prompt incl. the host read-back of the first token"},
         "device_ms_per_step": round(1e3 * dev_s / a.steps, 4),
         "step_bytes": int(step_bytes), "step_roofline_frac": round(step_bytes * (a.steps / t_all) / HBM_PEAK, 4),
-        # `frac` is what THIS process measured: HIP events on the launch stream around back-to-back launches of the kernel over every layer's weights (2.1 GB: nothing
-        # cache-resident).  The in-graph average of the committed rocprofv3 trace (launch boundary included) is the side object `in_graph`, quoted only when the profile
-        # was taken from this very build (source digest).
-        "roofline": {"bound": "hbm", "kernel": "dec_gemv_kernel<1, EPI_GLU> (decode engine gate/up phase: RMSNorm + Q8_K quantize + gate/up GEMV + SiLU*up)",
-                     "achieved": round(achieved / 1e9, 1), "peak": HBM_PEAK / 1e9, "unit": "GB/s", "frac": round(achieved / HBM_PEAK, 4),
-                     "bytes_per_launch": int(kern_bytes), "us_per_launch": round(kern_s * 1e6, 2),
-                     "frac_source": "live: HIP events on the launch stream over back-to-back launches of every layer's weights, this process", "source_digest": source_digest(),
-                     **committed_profile(name, a.quant)},
         "greedy_tokens_head": [int(t) for t in toks[a.warmup: a.warmup + 8]],
     }
-    rl = out["roofline"]
-    if rl.get("in_graph"):
-        rl["in_graph"]["achieved"] = round(kern_bytes / (rl["in_graph"]["us_per_launch"] * 1e-6) / 1e9, 1)
-        rl["in_graph"]["frac"] = round(kern_bytes / (rl["in_graph"]["us_per_launch"] * 1e-6) / HBM_PEAK, 4)
+    if roofline is not None:
+        out["roofline"] = roofline
     if ttft_bf16 is not None:
         out["prefill_bf16"] = {"tokens_per_sec": round(a.prompt_len / ttft_bf16, 1), "ttft_ms": round(1e3 * ttft_bf16, 2), "frac": round(prefill_flops / ttft_bf16 / MFMA_PEAK, 4),
                                "gemm": ("hipBLASLt bf16 x bf16 -> f32 on a bf16 shadow copy of the dense linears (dequantized once at load: 2 bytes per weight)" if model.bf16_shadow
@@ -848,7 +881,7 @@ def main():
                                        "only close to (not identical with) the decode engine's -- the default keeps the reference CPU arithmetic"}
     if ar is not None:
         out["allreduce"] = ar
-    if world == 1 and B == 1 and not a.no_dropin and not a.small and a.quant == "q4_k_m" and not moe:
+    if a.full and world == 1 and B == 1 and not a.no_dropin and not a.small and a.quant == "q4_k_m" and not moe:
         try:
             d_tok, d_frac = dropin_rate(model, cfg, prompt, min(a.steps, 64), dev)
             out["dropin_tokens_per_sec"] = round(d_tok, 2)
@@ -857,14 +890,14 @@ def main():
         except Exception as e:
             out["dropin_tokens_per_sec"] = None
             out["dropin_note"] = f"failed: {e}"
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         try:
             out["cpu_baseline"], par = parity_leg(model, cfg, a, prefill_exact)
             out.update(par)
         except Exception as e:  # the baseline is a reported extra, never fatal
             import traceback
             out["cpu_baseline"] = {"value": None, "unit": "tokens/s", "cores": 0, "kind": "port", "sample": f"failed: {e}: {traceback.format_exc()[-400:]}"}
-    if rank == 0 and world == 1 and not a.no_extra and not a.small and B == 1 and a.quant == "q4_k_m" and not moe and cfg.max_batch >= 8 and not a.shard_shapes:
+    if a.full and rank == 0 and world == 1 and not a.no_extra and not a.small and B == 1 and a.quant == "q4_k_m" and not moe and cfg.max_batch >= 8 and not a.shard_shapes:
         # side field, never fatal: the same model decoding 4 and 8 sequences per step (the reference's MMVQ contract: batch 1-8 from one weight pass, mmvq_gguf.cu:724-792;
         # what the scheduler feeds).  `value` stays the batch-1 line BASELINE.json names.
         try:
@@ -876,7 +909,7 @@ def main():
                                                   "step_roofline_frac": round(model.decode_bytes(bb, int(a.prompt_len + bw + bs_ / 2)) * (bs_ / rb["t_all"]) / HBM_PEAK, 4)}
         except Exception as e:
             out["batched_decode"] = {"failed": f"{type(e).__name__}: {e}"}
-    if rank == 0 and world == 1 and not a.no_extra and not a.small and B == 1 and a.quant == "q4_k_m" and a.model in ("auto", "8b") and not a.shard_shapes:
+    if a.full and rank == 0 and world == 1 and not a.no_extra and not a.small and B == 1 and a.quant == "q4_k_m" and a.model in ("auto", "8b") and not a.shard_shapes:
         out["extra_configs"] = {}
         del model
         import gc

@@ -5,7 +5,7 @@
 set -u
 OUT=gpurun_out/occ4
 mkdir -p $OUT
-run() { tag=$1; shift; (env "$@" timeout 300 python bench.py --no-cpu-baseline --steps 128 2>&1 | tail -1) > $OUT/$tag.json; python - "$OUT/$tag.json" "$tag" <<'PY'
+run() { tag=$1; shift; (env "$@" timeout 300 python bench.py --full --no-cpu-baseline --steps 128 2>&1 | tail -1) > $OUT/$tag.json; python - "$OUT/$tag.json" "$tag" <<'PY'
 import json, sys
 try:
     j = json.loads(open(sys.argv[1]).read())

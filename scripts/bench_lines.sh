@@ -5,7 +5,7 @@ cd /root/repo
 export TMPDIR=/tmp
 bash scripts/profile_round.sh round3
 O=gpurun_out/round3
-run() { name=$1; shift; (timeout 500 python bench.py --no-cpu-baseline --no-dropin "$@" 2>&1 | tail -1) > $O/line_$name.log; python - "$O/line_$name.log" "$name" <<'PY'
+run() { name=$1; shift; (timeout 500 python bench.py --full --no-cpu-baseline --no-dropin "$@" 2>&1 | tail -1) > $O/line_$name.log; python - "$O/line_$name.log" "$name" <<'PY'
 import json, sys
 try:
     j = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -52,7 +52,7 @@ def main():
     table = subprocess.run([sys.executable, os.path.join(root, "scripts", "rocprof_summary.py"), kt, "--top", "40", "--match", "mrs::"],
                            capture_output=True, text=True, check=True).stdout
     with open(os.path.join(root, "profiles", f"{tag}_kernel_stats.md"), "w") as f:
-        f.write(f"# {tag}: `rocprofv3 --kernel-trace --stats -- python bench.py --no-cpu-baseline --no-extra` (MI355X, per-kernel, mrs:: kernels)\n\n")
+        f.write(f"# {tag}: `rocprofv3 --kernel-trace --stats -- python bench.py --full --no-cpu-baseline --no-extra` (MI355X, per-kernel, mrs:: kernels)\n\n")
         f.write(table)
     # per-kernel average durations of the same pass as JSON (bench.py reads the dominant kernel's IN-GRAPH time from it: inside a captured graph the start / end stamps
     # of consecutive kernels touch, so these durations include the launch boundary that the HIP-event figure of bench.py's `roofline` does not)
@@ -61,7 +61,7 @@ def main():
         ks = {r["Name"]: {"calls": int(r["Calls"]), "avg_us": float(r["AverageNs"]) / 1e3, "min_us": float(r["MinNs"]) / 1e3, "max_us": float(r["MaxNs"]) / 1e3}
               for r in csv.DictReader(open(stats[0])) if "mrs::" in r["Name"]}
         with open(os.path.join(root, "profiles", f"{tag}_kernel_stats.json"), "w") as f:
-            json.dump({"source": "rocprofv3 --kernel-trace --stats -- python bench.py --no-cpu-baseline --no-extra (decode graph replays + the prompt)",
+            json.dump({"source": "rocprofv3 --kernel-trace --stats -- python bench.py --full --no-cpu-baseline --no-extra (decode graph replays + the prompt)",
                        "source_digest": digest, "commit": commit, "kernels": ks}, f, indent=1, sort_keys=True)
     fetch, write = counters(os.path.join(src, "fetch"), "FETCH_SIZE"), counters(os.path.join(src, "write"), "WRITE_SIZE")
     out = {}
@@ -71,7 +71,7 @@ def main():
         w = write.get(k, [0.0])
         out[k] = {"launches": len(v), "fetch_size_kb_avg": sum(v) / len(v), "read_bytes_per_launch": 2.0 * 1024.0 * sum(v) / len(v),
                   "write_size_kb_avg": sum(w) / len(w), "write_bytes_per_launch": 1024.0 * sum(w) / len(w)}
-    meta = {"source": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE (separate passes) -- python bench.py --no-cpu-baseline --no-dropin --steps 32",
+    meta = {"source": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE (separate passes) -- python bench.py --full --no-cpu-baseline --no-dropin --steps 32",
             "correction": "FETCH_SIZE is in KB and counts 64 B per 128-B request on gfx950 for wide coalesced reads: read bytes = 2 * 1024 * FETCH_SIZE",
             "source_digest": digest, "commit": commit, "kernels": out}
     with open(os.path.join(root, "profiles", f"{tag}_hbm_traffic.json"), "w") as f:
