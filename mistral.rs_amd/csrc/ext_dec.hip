@@ -112,7 +112,7 @@ static bool make_mat(Mat &m, const void *planes, int type, long long n, long lon
 
 // ------------------------------------------------------------------------------------------------ decode attention, split + last-arriver merge
 // Grid (kv heads, sequences, splits), G waves per workgroup = the G query heads of ONE split (round 5; rounds 3-4: 4 splits per workgroup, all G heads per
-// wave), no barrier in the split phase.  TICKET variant: instead of a second launch for the merge (4.9 us + a kernel boundary per layer), every workgroup publishes its
+// wave), no barrier in the split phase.  Instead of a second launch for the merge (4.9 us + a kernel boundary per layer), every workgroup publishes its
 // partials write-through at agent scope, drains its stores and takes a ticket on the (sequence, kv head) counter; the workgroup that draws the
 // last ticket merges all G heads of the kv head: wave w = query heads 2w, 2w + 1 (256 output values = ONE Q8_K superblock of the attention
 // vector), lane = 4 consecutive dims, sequential over the splits (attn_merge_core's order).  It writes the f32 result and -- what o_proj's
@@ -125,8 +125,8 @@ struct Attn2Args {
   uint8_t *img;      // Q8_K image of [seqs] columns of num_heads * 128 values, or nullptr (odd GQA groups: the caller's o_proj quantizes)
 };
 // merge of one (sequence, kv head): wave w <-> query heads (2w, 2w + 1) of the group (G == 1: wave 0, one head in lanes 0..31), lane = 4 consecutive
-// dims, sequential over the splits.  AGENT: the partials were published by other workgroups of the SAME launch (sc1 loads); else plain loads.
-template <int G, bool AGENT>
+// dims, sequential over the splits.  The partials were published by other workgroups of the SAME launch: sc1 loads.
+template <int G>
 __device__ __forceinline__ void attn2_merge(const Attn2Args &a, int kvh, int seq, int ns, int wave, int lane, int ncols) {
   constexpr int HD = 128, NP = (G + 1) / 2;
   const AttnArgs &t = a.t;
@@ -135,7 +135,7 @@ __device__ __forceinline__ void attn2_merge(const Attn2Args &a, int kvh, int seq
   const bool live = 2 * wave + hsel < G;
   const size_t pA = ((size_t)seq * t.num_heads + head0 + 2 * wave) * t.max_splits;                 // partials of head A (lanes 0..31)
   const size_t pB = ((size_t)seq * t.num_heads + head0 + min(2 * wave + 1, G - 1)) * t.max_splits;  // head B (lanes 32..63)
-  auto ldw = [&](const float *p) { if constexpr (AGENT) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); else return *p; };
+  auto ldw = [&](const float *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
   const float mA = lane < ns ? ldw(t.part_m + pA + lane) : -FLT_MAX, lA = lane < ns ? ldw(t.part_l + pA + lane) : 0.f;
   const float mB = lane < ns ? ldw(t.part_m + pB + lane) : -FLT_MAX, lB = lane < ns ? ldw(t.part_l + pB + lane) : 0.f;
   // one descriptor for both heads' partials (wave-uniform); the lanes of head B add its distance.  The partial outputs of up to 16 splits are
@@ -143,7 +143,7 @@ __device__ __forceinline__ void attn2_merge(const Attn2Args &a, int kvh, int seq
   const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc((void *)(t.part_o + pA * HD), (short)0, (int)((pB - pA + ns) * HD * 4), 0x00020000);
   const unsigned off0 = (unsigned)(lane & 31) * 16u + (hsel ? (unsigned)((pB - pA) * HD * 4) : 0u);
   constexpr int MB = 16;
-  constexpr int AUX = AGENT ? 16 : 0;
+  constexpr int AUX = 16;  // sc1
   v4u r[MB];
 #pragma unroll
   for (int i = 0; i < MB; ++i) r[i] = __builtin_amdgcn_raw_buffer_load_b128(ro, off0 + (unsigned)i * 512u, 0, AUX);  // past the last split of head B: out of range, zeros
@@ -179,11 +179,11 @@ __device__ __forceinline__ void attn2_merge(const Attn2Args &a, int kvh, int seq
   }
 }
 
-// TICKET: one launch (the last workgroup of a (sequence, kv head) merges); else the split phase only and dec_attn2_merge_kernel follows.
+// One launch: the last workgroup of a (sequence, kv head) merges.
 // Round 5 geometry: grid (kv heads, sequences, splits), G waves per workgroup: wave g = query head head0 + g of ONE split (round 4: 4 splits per workgroup, every wave
 // all G heads: 56 workgroups of 329 VGPRs at a 512-token context).  The per-head arithmetic is the same function (attn_split_core<1>): same bits; the G waves read the
 // same 16 KB of K / V (L1 / L2 hits), every wave's serial chain is 1 / G as long, and a 512-token context fills 8 x 24 = 192 CUs.
-template <int G, class CT, bool TICKET>
+template <int G, class CT>
 __global__ void __launch_bounds__(64 * G) dec_attn2_kernel(const Attn2Args a) {
   constexpr int HD = 128;
   __shared__ __attribute__((aligned(16))) float q_s[G][HD + 32];
@@ -202,17 +202,11 @@ __global__ void __launch_bounds__(64 * G) dec_attn2_kernel(const Attn2Args a) {
     const int ctx_w = (int)t.context_lens[seq], lo_w = t.window > 0 && ctx_w > t.window ? ctx_w - t.window : 0;
     auto publish = [&](int, float o0, float o1, float m, float l) {
       const size_t pi = ((size_t)seq * t.num_heads + head0 + wave) * t.max_splits + split;
-      if constexpr (TICKET) {
-        __hip_atomic_store(t.part_o + pi * HD + lane, o0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(t.part_o + pi * HD + lane + 64, o1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (lane == 0) {
-          __hip_atomic_store(t.part_m + pi, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          __hip_atomic_store(t.part_l + pi, l, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-      } else {
-        t.part_o[pi * HD + lane] = o0;
-        t.part_o[pi * HD + lane + 64] = o1;
-        if (lane == 0) { t.part_m[pi] = m; t.part_l[pi] = l; }
+      __hip_atomic_store(t.part_o + pi * HD + lane, o0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(t.part_o + pi * HD + lane + 64, o1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (lane == 0) {
+        __hip_atomic_store(t.part_m + pi, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(t.part_l + pi, l, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
     };
     if (b1 * 32 <= lo_w) {  // every block of the split lies before the sliding window: the partial a fully masked pass would give, without reading K / V
@@ -221,31 +215,20 @@ __global__ void __launch_bounds__(64 * G) dec_attn2_kernel(const Attn2Args a) {
       attn_split_core<1, CT>(t, kvh, head0 + wave, seq, b0, b1, q_s[wave], q_s[wave] + HD, publish, (int)blk_first);
     }
   }
-  if constexpr (TICKET) {
-    MRS_WAIT_VMCNT0();  // this wave's partials have left the CU
-    __syncthreads();
-    unsigned *tk = a.ticket + (size_t)seq * t.num_kv_heads + kvh;
-    // The ticket's ordering is a build-time choice (MRS_DEC_ATTN_TICKET_ORDER, default __ATOMIC_RELAXED since round 5).  The hand-off is the guide's R1 form
-    // (MI355X_MICROARCH.md, "Valid forms": sc1 write-through payload stores -> drained vmcnt(0) -> agent-scope flag; consumer: returned atomic -> sc1 loads, which never
-    // read the CU's L1): the payload is already in memory when the ticket is drawn, and the merge reads it past L1.  An ACQ_REL ticket (rounds 3-4) adds
-    // `buffer_wbl2 sc1` + `buffer_inv sc1` around the atomic in EVERY workgroup -- ~1.7 us each by the guide's price list, on the serial chain of the last arriver --
-    // and orders nothing this protocol relies on (no dirty lines to write back, no L1-served load to invalidate for).
-#ifndef MRS_DEC_ATTN_TICKET_ORDER
-#define MRS_DEC_ATTN_TICKET_ORDER __ATOMIC_RELAXED
-#endif
-    if (tid == 0) last_s = __hip_atomic_fetch_add(tk, 1u, MRS_DEC_ATTN_TICKET_ORDER, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)(ns - 1);
-    __syncthreads();
-    if (!last_s) return;
-    if (tid == 0) __hip_atomic_store(tk, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // every other workgroup of this (seq, kv head) has already drawn
-    attn2_merge<G, true>(a, kvh, seq, ns, wave, lane, gridDim.y);
-  }
-}
-// the merge as its own launch: grid (kv heads, sequences), (G + 1) / 2 waves
-template <int G>
-__global__ void __launch_bounds__(64 * ((G + 1) / 2)) dec_attn2_merge_kernel(const Attn2Args a) {
-  const int tid = tid_opaque(), lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int nblk = ((int)a.t.context_lens[blockIdx.y] + 31) / 32;
-  attn2_merge<G, false>(a, blockIdx.x, blockIdx.y, (nblk + a.t.bpw - 1) / a.t.bpw, wave, lane, gridDim.y);
+  MRS_WAIT_VMCNT0();  // this wave's partials have left the CU
+  __syncthreads();
+  unsigned *tk = a.ticket + (size_t)seq * t.num_kv_heads + kvh;
+  // The ticket is a relaxed agent-scope atomic (round 5).  The hand-off is the guide's R1 form (MI355X_MICROARCH.md, "Valid forms": sc1 write-through payload
+  // stores -> drained vmcnt(0) -> agent-scope flag; consumer: returned atomic -> sc1 loads, which never read the CU's L1): the payload is already in memory when the
+  // ticket is drawn, and the merge reads it past L1.  An ACQ_REL ticket (rounds 3-4) adds `buffer_wbl2 sc1` + `buffer_inv sc1` around the atomic in EVERY
+  // workgroup -- ~1.7 us each by the guide's price list, on the serial chain of the last arriver -- and orders nothing this protocol relies on (no dirty lines to
+  // write back, no L1-served load to invalidate for).
+  constexpr int ticket_order = __ATOMIC_RELAXED;
+  if (tid == 0) last_s = __hip_atomic_fetch_add(tk, 1u, ticket_order, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)(ns - 1);
+  __syncthreads();
+  if (!last_s) return;
+  if (tid == 0) __hip_atomic_store(tk, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // every other workgroup of this (seq, kv head) has already drawn
+  attn2_merge<G>(a, kvh, seq, ns, wave, lane, gridDim.y);
 }
 
 
@@ -540,25 +523,14 @@ extern "C" int mrs_dec_attention(float *out_f32, void *img_out, unsigned *ticket
   t.window = sliding_window > 0 ? sliding_window : 0;
   const int nblk = (max_context_len + 31) / 32;
   t.bpw = nblk <= 64 ? 1 : (nblk + 63) / 64;                        // == dec_bpw() of paged_attention.hip: at most 64 splits
-  { static const int force = [] { const char *e = getenv("MRS_DEC_ATTN_BPW"); return e ? atoi(e) : 0; }(); if (force > 0) t.bpw = force; }  // measurements only: the oracle's order follows the rule above
-  t.max_splits = mrs_decode_attention_max_splits(max_context_len);  // stride of the partials, as in the two-launch route
+  t.max_splits = mrs_decode_attention_max_splits(max_context_len);  // stride of the partials, as in mrs_decode_attention_f32_*
   a.ticket = ticket; a.img = with_img ? (uint8_t *)img_out : nullptr;
   const int nsplit = (nblk + t.bpw - 1) / t.bpw;
   const dim3 grid(num_kv_heads, num_seqs, nsplit);
   hipStream_t s = (hipStream_t)stream;
-  // MRS_DEC_ATTN_TICKET (default 1): the merge inside the split launch (last arriver); 0 = a second launch for the merge.  Measured on the MI355X
-  // (profiles/round3_decode.md): the hand-off (write-through partials, drain, device-scope ticket, sc1 loads) costs about what the second launch and its
-  // boundary cost -- 472.8 vs 465.4 tok/s for the whole step
-  static const int one_launch = [] { const char *e = getenv("MRS_DEC_ATTN_TICKET"); return e ? atoi(e) : 1; }();
-  const dim3 mgrid(num_kv_heads, num_seqs);
-#define MRS_A2(GG, CT)                                                                                                   \
-  do {                                                                                                                   \
-    if (one_launch) hipLaunchKernelGGL((dec_attn2_kernel<GG, CT, true>), grid, dim3(64 * GG), 0, s, a);                      \
-    else {                                                                                                               \
-      hipLaunchKernelGGL((dec_attn2_kernel<GG, CT, false>), grid, dim3(64 * GG), 0, s, a);                                   \
-      hipLaunchKernelGGL((dec_attn2_merge_kernel<GG>), mgrid, dim3(64 * ((GG + 1) / 2)), 0, s, a);                       \
-    }                                                                                                                    \
-  } while (0)
+  // The merge runs inside the split launch (last arriver).  Measured on the MI355X against a second launch for the merge (profiles/round3_decode.md): the hand-off
+  // (write-through partials, drain, device-scope ticket, sc1 loads) costs about what the second launch and its boundary cost -- 472.8 vs 465.4 tok/s for the whole step
+#define MRS_A2(GG, CT) hipLaunchKernelGGL((dec_attn2_kernel<GG, CT>), grid, dim3(64 * GG), 0, s, a)
 #define MRS_A2G(CT) switch (G) { case 1: MRS_A2(1, CT); break; case 2: MRS_A2(2, CT); break; case 4: MRS_A2(4, CT); break; default: MRS_A2(8, CT); break; }
   if (kv_dtype == 1) { MRS_A2G(bf16_t) } else { MRS_A2G(f16_t) }
 #undef MRS_A2G

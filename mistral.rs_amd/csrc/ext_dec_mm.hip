@@ -511,7 +511,7 @@ static int launch(const MmArgs &a0, hipStream_t s) {
   if (a.K <= 0 || a.K % 256 || a.nc < 1 || a.nc > 8 || !a.img || a.units < 1) return -1;
   const size_t lds = (lds_bytes(a.K, a.nc, a.mode) + 15) & ~(size_t)15;
   if (lds > (size_t)158 * 1024) return -2;
-  static const int wg_per_cu = [] { const char *e = getenv("MRS_DEC_MM_WG_PER_CU"); return e ? std::max(1, atoi(e)) : 2; }();
+  constexpr int wg_per_cu = 2;
   const int fit = (tmask == TM_Q4K || tmask == TM_Q5K || tmask == TM_Q80) ? 2 : 1;  // workgroups per CU the kernel's registers admit (see the kernels above)
   const int cap = 256 * std::min<int>(std::min(wg_per_cu, fit), std::max<size_t>(1, ((size_t)160 * 1024) / lds));
   const int grid = std::min(a.units, cap);

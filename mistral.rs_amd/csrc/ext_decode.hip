@@ -147,7 +147,7 @@ __device__ __forceinline__ size_t hot_row_bytes(int t, int K) {
 
 // MRS_DECODE_MIN_WAVES (build-time experiment knob, default off = the measured round-1 object code): the minimum number of waves per SIMD the
 // register allocator must leave room for.  4 caps the kernel at 128 VGPRs so that TWO 512-thread workgroups share a CU (16 waves per CU instead
-// of 8); pair it with MRS_PROJ_WGS=512 / MRS_GLU_PER=32 / MRS_QKV_PPW at run time.  profiles/round1_decode_kernel_resources.md has the numbers.
+// of 8); pair it with MRS_PROJ_WGS=512 at run time.  profiles/round1_decode_kernel_resources.md has the numbers.
 #ifdef MRS_DECODE_MIN_WAVES
 #define MRS_DECODE_BOUNDS(NT) __launch_bounds__(NT, MRS_DECODE_MIN_WAVES)
 #else
@@ -326,13 +326,11 @@ template <int PRO, int EPI> struct DecodeLaunch {
     int per;
     if (EPI == EPI_GLU_Q8_1) {
       per = 32 * ((total / 32 + 255) / 256);  // whole Q8_1 output blocks per workgroup, <= 256 workgroups
-      { static int ov = -1; if (ov < 0) { const char *e = getenv("MRS_GLU_PER"); ov = e ? atoi(e) : 0; } if (ov > 0) per = ov; }
       if (per < 32) per = 32;
     } else if (EPI == EPI_QKV_ROPE) {
       int ppw = (total / 2 + NW * 192 - 1) / (NW * 192);  // RoPE pairs per wave: <= 192 fat workgroups (measured optimum for 6144 rows)
       if (ppw < 1) ppw = 1;
       if (ppw > 64) ppw = 64;  // epilogue operands are prefetched one pair per lane
-      { static int ov = -1; if (ov < 0) { const char *e = getenv("MRS_QKV_PPW"); ov = e ? atoi(e) : 0; } if (ov > 0) ppw = ov; }
       per = 2 * NW * ppw;
       while (per > 2 * NW && (a.nrows[0] % per || a.nrows[1] % per)) per -= 2 * NW;
       if (a.nrows[0] % per || a.nrows[1] % per) return -3;  // a workgroup must not straddle q/k/v

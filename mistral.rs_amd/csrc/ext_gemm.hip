@@ -844,8 +844,7 @@ template <int TYPE, int NI> static void gemm_b_launch_ni(GemmBArgs a, size_t ws_
   for (int i = 0; i < a.nseg; ++i) { a.tile0[i] = tiles; tiles += (a.N[i] + TN - 1) / TN; n4 = n4 && a.N[i] % 4 == 0 && a.ldo[i] % 4 == 0; }
   const int mt = (a.M + HM - 1) / HM, nk = a.K / HK;
   int splits = 1;
-  if (const char *e = getenv("MRS_GEMM_SPLITS")) splits = atoi(e);
-  else if (tiles * mt < 192) splits = std::min(std::min(8, 256 / (tiles * mt)), std::max(1, nk / 8));
+  if (tiles * mt < 192) splits = std::min(std::min(8, 256 / (tiles * mt)), std::max(1, nk / 8));
   a.ldp = tiles * TN;
   a.tn = TN;
   if (!n4 || !a.partial) splits = 1;

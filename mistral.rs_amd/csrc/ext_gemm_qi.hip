@@ -757,7 +757,7 @@ static int gemm_qi_launch(const void *w_qi, int type, int N, int K, const void *
   a.qf = qf; a.yd = yd; a.bsf = bsf; a.out = out; a.ldo = ldo; a.accumulate = accumulate; a.win = win;
   dim3 grid((N + qi::TN - 1) / qi::TN, (max_rows + qi::TT - 1) / qi::TT);
   // few workgroups (o_proj / down_proj of a 512-token prompt: 128): one workgroup per run of superblocks, then the reduce -- the same additions in the same order
-  static const int split_max = [] { const char *e = getenv("MRS_GEMM_QI_SPLIT_BELOW"); return e ? atoi(e) : 200; }();
+  constexpr int split_max = 200;
   a.ksplit = 1; a.part = nullptr;
   if (!win && (int)(grid.x * grid.y) < split_max && K / 256 >= 4 && N % 4 == 0 && workspace && workspace_bytes >= (size_t)4 * T * N * 4) { a.ksplit = 4; a.part = (float *)workspace; grid.z = 4; }
   if (type == T_Q8_0) { auto kern = qi::gemm_q80_kernel; lds_attr_once((const void *)kern, 158 * 1024); hipLaunchKernelGGL(kern, grid, dim3(qi::GT), qi::L8_TOTAL, (hipStream_t)stream, a); }
@@ -1177,20 +1177,18 @@ extern "C" int mrs_prefill_attention_exact(const float *q, const void *k_cache, 
   // (w_j, l_j) per split live in LDS: as many splits as the longest context of this prompt needs (<= 64 by the rule above)
   const int need_ctx = max_prompt_ctx > 0 && max_prompt_ctx < max_context_len ? max_prompt_ctx : max_context_len;
   a.max_splits = std::max(1, std::min(64, (((need_ctx + 31) / 32) + a.bpw - 1) / a.bpw));
-  // round 6: the matrix-core form (prefill_attn_mfma_kernel: the same chains on v_mfma_f32_32x32x2_f32); MRS_PREFILL_ATTN_MFMA=0 keeps the vector-ALU kernel
-  static const int use_mfma = [] { const char *e = getenv("MRS_PREFILL_ATTN_MFMA"); return e ? atoi(e) : 1; }();
+  // round 6: the matrix-core form (prefill_attn_mfma_kernel: the same chains on v_mfma_f32_32x32x2_f32); contexts whose LDS does not fit take the vector-ALU kernel below
   {
     const int nb = (need_ctx + 31) / 32;
     const size_t lds_m = (size_t)mrs::qi::PM_Q + mrs::qi::PM_P + mrs::qi::PM_SC + (size_t)nb * 128;
-    if (use_mfma && lds_m <= 158 * 1024) {
+    if (lds_m <= 158 * 1024) {
       const dim3 gm(num_heads, (T + 31) / 32);
       if (kv_dtype == 1) { auto kern = mrs::qi::prefill_attn_mfma_kernel<mrs::bf16_t>; mrs::lds_attr_once((const void *)kern, 158 * 1024); hipLaunchKernelGGL(kern, gm, dim3(64 * mrs::qi::PM_NW), lds_m, (hipStream_t)stream, a, nb); }
       else { auto kern = mrs::qi::prefill_attn_mfma_kernel<mrs::f16_t>; mrs::lds_attr_once((const void *)kern, 158 * 1024); hipLaunchKernelGGL(kern, gm, dim3(64 * mrs::qi::PM_NW), lds_m, (hipStream_t)stream, a, nb); }
       return 0;
     }
   }
-  static const int qw_env = [] { const char *e = getenv("MRS_PREFILL_ATTN_QW"); return e ? atoi(e) : 0; }();
-  int qw = qw_env > 0 ? qw_env : 4;  // prompt tokens per wave
+  int qw = 4;  // prompt tokens per wave
   auto lds_for = [&](int w) { return 4 * ((size_t)w * G * 128 * 2 + (size_t)G * 32 + (size_t)w * G * a.max_splits * 2 + (size_t)w * G * 64) * 4; };
   while (qw > 1 && (lds_for(qw) > 76 * 1024 || (T + 4 * qw - 1) / (4 * qw) * num_kv_heads < 512)) --qw;  // two workgroups per CU, and enough workgroups to fill the chip
   const size_t lds = lds_for(qw);

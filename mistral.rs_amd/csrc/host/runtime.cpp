@@ -199,7 +199,6 @@ class Llama {
   mrs_llama_buffers bufs{};
   Workspace ws{};
   bool have_bufs = false;
-  int attn2 = [] { const char *e = getenv("MRS_DEC_ATTN2"); return e ? atoi(e) : 1; }();  // decode engine attention: 1 = split kernel with the last-arriver merge + Q8_K image for o_proj (round 3, one launch), 0 = split + merge launches
   void *comm = nullptr;  // RCCL communicator (ext_comm.hip) when cfg.world_size > 1
   void *p2p = nullptr;   // one-shot peer-mailbox all-reduce (ext_p2p.hip) for decode-sized messages
 
@@ -355,34 +354,29 @@ class Llama {
   }
 
   // ---- MI355X fused sequence: 5 launches per layer (+ attention reduce / quantize)
-  // experiment hook (scripts/exp): MRS_ABLATE bit mask skips kernel classes so their in-graph cost can be measured
-  static int ablate() { static int v = -1; if (v < 0) { const char *e = getenv("MRS_ABLATE"); v = e ? atoi(e) : 0; } return v; }
   int forward_fused(int b, hipStream_t s) const {
-    const int ab = ablate();
     const float rs = 1.0f / (float)std::max(1, (int)cfg.world_size);
     const int d = cfg.hidden_size, hd = cfg.head_dim, nq = cfg.num_heads * hd, nkv = cfg.num_kv_heads * hd, ff = cfg.intermediate_size;
     const int stride_q = pad_to(nq, MATRIX_ROW_PADDING) / 32, stride_f = pad_to(ff, MATRIX_ROW_PADDING) / 32;
     if (wte->embedding_forward_raw(bufs.input_ids, b, ws.h, s)) return -1;
     for (const Block &bl : blocks) {
       const QTensor *q = bl.q_proj->get_qtensor(), *k = bl.k_proj->get_qtensor(), *v = bl.v_proj->get_qtensor();
-      if (!(ab & 1) && mrs_decode_qkv(q->data, k->data, v->data, q->dtype, k->dtype, v->dtype, nq, nkv, nkv, d, ws.h, bl.input_layernorm,
+      if (mrs_decode_qkv(q->data, k->data, v->data, q->dtype, k->dtype, v->dtype, nq, nkv, nkv, d, ws.h, bl.input_layernorm,
                          cfg.rms_eps, ws.q, bl.key_cache, bl.value_cache, bufs.slot_mapping, bufs.positions, bufs.cos_table,
                          bufs.sin_table, hd, cfg.rot_dim / 2, cfg.num_kv_heads, cfg.block_size, b, s))
         return fail("mrs_decode_qkv refused the layer");
-      if (!(ab & 2)) {
-        const int bs = cfg.block_size, kvh = cfg.num_kv_heads;
-        const int eff_max = std::min(cfg.max_blocks_per_seq * bs, cfg.max_context_len);
-        if (mrs_decode_attention_q8_1_f32_bf16(ws.y_a, stride_q, ws.exp_sums, ws.max_logits, ws.attn_ws, ws.q, bl.key_cache, bl.value_cache, kvh,
-                                               1.0f / sqrtf((float)hd), bufs.block_tables, bufs.context_lens, bs, eff_max, b, cfg.num_heads, hd,
-                                               cfg.max_blocks_per_seq, cfg.num_heads * hd, kvh * hd * bs, hd * bs, s)) {
-          paged_attention_decode(bl, b, s);  // shapes outside the split kernel: reference-partitioned attention + quantize
-          mrs_quantize_rows_q8_1(ws.attn, ws.y_a, nq, stride_q, b, s);
-        }
+      const int bs = cfg.block_size, kvh = cfg.num_kv_heads;
+      const int eff_max = std::min(cfg.max_blocks_per_seq * bs, cfg.max_context_len);
+      if (mrs_decode_attention_q8_1_f32_bf16(ws.y_a, stride_q, ws.exp_sums, ws.max_logits, ws.attn_ws, ws.q, bl.key_cache, bl.value_cache, kvh,
+                                             1.0f / sqrtf((float)hd), bufs.block_tables, bufs.context_lens, bs, eff_max, b, cfg.num_heads, hd,
+                                             cfg.max_blocks_per_seq, cfg.num_heads * hd, kvh * hd * bs, hd * bs, s)) {
+        paged_attention_decode(bl, b, s);  // shapes outside the split kernel: reference-partitioned attention + quantize
+        mrs_quantize_rows_q8_1(ws.attn, ws.y_a, nq, stride_q, b, s);
       }
       const QTensor *o = bl.o_proj->get_qtensor();
       // TP: h <- h / world + W_o . attn on every rank, then ONE sum all-reduce of h gives h + sum of the partials (division by a
       // power of two is exact), so the residual add stays fused and nothing else crosses GPUs
-      if (!(ab & 4) && (mrs_decode_proj_scaled(o->data, o->dtype, d, nq, ws.y_a, stride_q, ws.h, d, rs, b, s) || all_reduce(ws.h, (size_t)b * d, s))) return fail("o_proj failed: %s", g_last_error.c_str());
+      if (mrs_decode_proj_scaled(o->data, o->dtype, d, nq, ws.y_a, stride_q, ws.h, d, rs, b, s) || all_reduce(ws.h, (size_t)b * d, s)) return fail("o_proj failed: %s", g_last_error.c_str());
       if (cfg.num_experts > 0) {
         // SparseMoeBlock::forward (models/mixtral.rs:280-304): router on the normed hidden state, then per token the top-k experts'
         // fused gate/up (+SiLU*up -> Q8_1) and down GEMVs, accumulated into h with the renormalised routing weights.  Expert ids and
@@ -407,12 +401,12 @@ class Llama {
         continue;
       }
       const QTensor *g = bl.gate_proj->get_qtensor(), *u = bl.up_proj->get_qtensor(), *dn = bl.down_proj->get_qtensor();
-      if (!(ab & 8) && mrs_decode_gate_up(g->data, u->data, g->dtype, ff, d, ws.h, bl.post_attention_layernorm, cfg.rms_eps, 0, ws.y_b, stride_f, b, s))
+      if (mrs_decode_gate_up(g->data, u->data, g->dtype, ff, d, ws.h, bl.post_attention_layernorm, cfg.rms_eps, 0, ws.y_b, stride_f, b, s))
         return fail("mrs_decode_gate_up refused");
-      if (!(ab & 16) && (mrs_decode_proj_scaled(dn->data, dn->dtype, d, ff, ws.y_b, stride_f, ws.h, d, rs, b, s) || all_reduce(ws.h, (size_t)b * d, s))) return fail("down_proj failed: %s", g_last_error.c_str());
+      if (mrs_decode_proj_scaled(dn->data, dn->dtype, d, ff, ws.y_b, stride_f, ws.h, d, rs, b, s) || all_reduce(ws.h, (size_t)b * d, s)) return fail("down_proj failed: %s", g_last_error.c_str());
     }
     const QTensor *lm = lm_head->get_qtensor();
-    if (!(ab & 32) && mrs_decode_norm_proj(lm->data, lm->dtype, cfg.vocab_size, d, ws.h, ln_f, cfg.rms_eps, bufs.logits, cfg.vocab_size, b, s))
+    if (mrs_decode_norm_proj(lm->data, lm->dtype, cfg.vocab_size, d, ws.h, ln_f, cfg.rms_eps, bufs.logits, cfg.vocab_size, b, s))
       return fail("mrs_decode_norm_proj refused");
     return 0;
   }
@@ -444,13 +438,12 @@ class Llama {
     if (chained && b != 1) return fail("chained decode step: batch 1 only");
     if (!chained && wte->embedding_forward_raw(bufs.input_ids, b, ws.h, s)) return -1;
     // Batched steps: every GEMV workgroup would normalise + quantize all b activation columns itself (256 times the same work, 17-25 us of a 40-60 us launch at
-    // b = 8); from MRS_DEC_IMG_MIN_B columns on the image of a phase is built once by mrs_dec_act_image (b workgroups) and the GEMVs copy it -- same bytes.
-    static const int img_min_b = [] { const char *e = getenv("MRS_DEC_IMG_MIN_B"); return e ? atoi(e) : 2; }();
-    const bool imgb = b >= img_min_b && b >= 2 && b <= 8;
+    // b = 8); from 2 columns on the image of a phase is built once by mrs_dec_act_image (b workgroups) and the GEMVs copy it -- same bytes.
+    const bool imgb = b >= 2 && b <= 8;
     auto image = [&](const float *x, int ldx, const float *nw, int k, int wtype) { return mrs_dec_act_image(x, ldx, nw, cfg.rms_eps, k, wtype, b, ws.act_img, s); };
     // (round 6) batched steps on the matrix cores (ext_dec_mm.hip): the same launches on the MFMA-order copy of the weights the exact prompt path keeps (QTensor::qi) -- integer
-    // dots on v_mfma_i32_32x32x32_i8 instead of 535 VALU per 8-column tile, the same bits.  MRS_DEC_MM=0 keeps the vector-ALU kernels; MRS_DEC_MM_MIN_B: smallest batch that takes it.
-    static const int mm_min_b = [] { const char *e = getenv("MRS_DEC_MM"); if (e && atoi(e) == 0) return 1 << 30; const char *m = getenv("MRS_DEC_MM_MIN_B"); return m ? atoi(m) : 3; }();  // measured (MI355X, 8B Q4_K_M): batch 2 / 3 / 4 / 8 = 760 / 1128 / 1518 / 2722 tok/s here, 824 / 1103 / 1315 / 1685 on the vector ALU
+    // dots on v_mfma_i32_32x32x32_i8 instead of 535 VALU per 8-column tile, the same bits.  Batch 2 stays on the vector-ALU kernels.
+    constexpr int mm_min_b = 3;  // measured (MI355X, 8B Q4_K_M): batch 2 / 3 / 4 / 8 = 760 / 1128 / 1518 / 2722 tok/s here, 824 / 1103 / 1315 / 1685 on the vector ALU
     const bool mmb = imgb && b >= mm_min_b;
     auto qi_of = [](const std::unique_ptr<GgufMatMul> &l) -> const void * { return l && l->get_qtensor() ? l->get_qtensor()->qi : nullptr; };
     auto mm_ok = [&](const void *qi, int type, int k) { return mmb && qi && mrs_dec_mm_supported(type, k, b); };
@@ -469,26 +462,17 @@ class Llama {
       } else if ((cfg.rope_interleaved ? mrs_dec_qkv : mrs_dec_qkv_neox)(&bl.dq, &bl.dk, &bl.dv, ws.h, d, bl.input_layernorm, cfg.rms_eps, ws.q, bl.key_cache, bl.value_cache,
                                                                   bufs.slot_mapping, bufs.positions, bufs.cos_table, bufs.sin_table, hd, cfg.rot_dim / 2, kvh, bs, kvd, b, s))
         return fail("mrs_dec_qkv refused the layer");
-      if (attn2) {
-        // one launch: splits + last-arriver merge; even GQA groups hand o_proj the Q8_K image of the result (Q8_0 weights take Q8_0 activations: f32 result)
-        const bool want_img = bl.dout.type != 8 && (cfg.num_heads / kvh) % 2 == 0 && mrs_dec_act_image_bytes(nq, b) <= mrs_dec_proj_img_max_bytes();
-        const int rc2 = mrs_dec_attention(want_img ? nullptr : ws.attn, want_img ? ws.attn_img : nullptr, ws.attn_ticket, (float *)ws.attn_ws, ws.max_logits, ws.exp_sums, ws.q,
-                                          bl.key_cache, bl.value_cache, kvh, 1.0f / sqrtf((float)hd), bufs.block_tables, bufs.context_lens, bs, eff_max, b, cfg.num_heads, hd,
-                                          cfg.max_blocks_per_seq, nq, kvh * hd * bs, hd * bs, kvd, cfg.sliding_window, s);
-        if (rc2 < 0) return fail("mrs_dec_attention refused the shape");
-        const int prc = rc2 == 1 ? (mm_ok(qi_of(bl.o_proj), bl.dout.type, nq) ? mrs_dec_mm_proj(qi_of(bl.o_proj), bl.dout.type, d, nq, ws.attn_img, ws.h, d, 1, rs, b, s)
-                                                                                : mrs_dec_proj_img(&bl.dout, d, ws.attn_img, ws.h, d, 1, rs, b, s))
-                                 : mrs_dec_proj(&bl.dout, d, nullptr, ws.attn, nq, nullptr, 0.f, ws.h, d, 1, rs, nullptr, b, s);
-        if (prc || all_reduce(ws.h, (size_t)b * d, s)) return fail("o_proj failed (%d): %s", prc, g_last_error.c_str());
-      } else {
-        if (mrs_decode_attention_f32_f32_bf16(ws.attn, ws.exp_sums, ws.max_logits, ws.attn_ws, ws.q, bl.key_cache, bl.value_cache, kvh, 1.0f / sqrtf((float)hd),
-                                              bufs.block_tables, bufs.context_lens, bs, eff_max, b, cfg.num_heads, hd, cfg.max_blocks_per_seq, nq, kvh * hd * bs,
-                                              hd * bs, kvd, s))
-          return fail("mrs_decode_attention_f32 refused the shape");
-        // TP: h <- h / world + W_o . attn on every rank, then ONE sum all-reduce of h (the residual add stays fused, as in forward_fused)
-        if (mrs_dec_proj(&bl.dout, d, nullptr, ws.attn, nq, nullptr, 0.f, ws.h, d, 1, rs, nullptr, b, s) || all_reduce(ws.h, (size_t)b * d, s))
-          return fail("o_proj failed: %s", g_last_error.c_str());
-      }
+      // one launch: splits + last-arriver merge; even GQA groups hand o_proj the Q8_K image of the result (Q8_0 weights take Q8_0 activations: f32 result)
+      const bool want_img = bl.dout.type != 8 && (cfg.num_heads / kvh) % 2 == 0 && mrs_dec_act_image_bytes(nq, b) <= mrs_dec_proj_img_max_bytes();
+      const int rc2 = mrs_dec_attention(want_img ? nullptr : ws.attn, want_img ? ws.attn_img : nullptr, ws.attn_ticket, (float *)ws.attn_ws, ws.max_logits, ws.exp_sums, ws.q,
+                                        bl.key_cache, bl.value_cache, kvh, 1.0f / sqrtf((float)hd), bufs.block_tables, bufs.context_lens, bs, eff_max, b, cfg.num_heads, hd,
+                                        cfg.max_blocks_per_seq, nq, kvh * hd * bs, hd * bs, kvd, cfg.sliding_window, s);
+      if (rc2 < 0) return fail("mrs_dec_attention refused the shape");
+      // TP: h <- h / world + W_o . attn on every rank, then ONE sum all-reduce of h (the residual add stays fused, as in forward_fused)
+      const int prc = rc2 == 1 ? (mm_ok(qi_of(bl.o_proj), bl.dout.type, nq) ? mrs_dec_mm_proj(qi_of(bl.o_proj), bl.dout.type, d, nq, ws.attn_img, ws.h, d, 1, rs, b, s)
+                                                                              : mrs_dec_proj_img(&bl.dout, d, ws.attn_img, ws.h, d, 1, rs, b, s))
+                               : mrs_dec_proj(&bl.dout, d, nullptr, ws.attn, nq, nullptr, 0.f, ws.h, d, 1, rs, nullptr, b, s);
+      if (prc || all_reduce(ws.h, (size_t)b * d, s)) return fail("o_proj failed (%d): %s", prc, g_last_error.c_str());
       if (cfg.num_experts > 0) {
         // SparseMoeBlock::forward (models/mixtral.rs:280-304): router on the normed hidden state; per token the top-k experts' gate/up then down,
         // accumulated into h with the renormalised routing weights; expert ids / weights stay on the device
@@ -496,9 +480,7 @@ class Llama {
         // outputs, then ONE all-reduce per MoE block (the router is replicated: every rank picks the same experts)
         const int E = cfg.num_experts, tk = cfg.num_experts_per_tok;
         // (round 6) E workgroups per token + the last arriver's top-k: the same ids and weights as the one-workgroup router, bit for bit, without 8 router rows through one CU
-        static const bool split_router = [] { const char *e = getenv("MRS_MOE_ROUTER_SPLIT"); return !e || atoi(e) != 0; }();
-        const int rrc = split_router ? mrs_moe_router_topk_norm_split(ws.h, bl.post_attention_layernorm, cfg.rms_eps, bl.router, b, E, d, tk, 1, ws.moe_ids, ws.moe_w, ws.moe_router_scratch, s)
-                                     : mrs_moe_router_topk_norm(ws.h, bl.post_attention_layernorm, cfg.rms_eps, bl.router, b, E, d, tk, 1, ws.moe_ids, ws.moe_w, s);  // norm inside the router
+        const int rrc = mrs_moe_router_topk_norm_split(ws.h, bl.post_attention_layernorm, cfg.rms_eps, bl.router, b, E, d, tk, 1, ws.moe_ids, ws.moe_w, ws.moe_router_scratch, s);  // norm inside the router
         if (rrc == -3) {
           mrs_rms_norm_f32(ws.h, bl.post_attention_layernorm, ws.xn, b, d, cfg.rms_eps, (int64_t)(intptr_t)s);
           if (mrs_moe_router_topk(ws.xn, bl.router, b, E, d, tk, 1, ws.moe_ids, ws.moe_w, nullptr, s)) return fail("moe router refused (experts %d, top-k %d)", E, tk);
@@ -547,7 +529,7 @@ class Llama {
   //      of PagedAttention::forward).  Buffers are carved from the caller's prefill workspace.
   // prompts longer than this use the 256-row-tile GEMM over bf16 slabs (its L1-bypassing A loads beat the 128-row f32 kernel even when
   // half of the tile rows are empty: TTFT 16.3 -> 10.1 ms at T = 128, 19.5 -> 8.3 ms at T = 64, 18.5 -> 7.7 ms at T = 32)
-  static int prefill_big_min() { static int v = -1; if (v < 0) { const char *e = getenv("MRS_PREFILL_BIG_MIN"); v = e ? atoi(e) : 16; } return v; }
+  static constexpr int prefill_big_min = 16;
   static size_t prefill_workspace_bytes(const mrs_llama_config &c, int T) {
     const size_t t = (size_t)T, d = c.hidden_size, nq = (size_t)c.num_heads * c.head_dim, nkv = (size_t)c.num_kv_heads * c.head_dim;
     const size_t ff = c.intermediate_size;
@@ -558,7 +540,7 @@ class Llama {
     b += align(t * ff * 4) * 3;       // gate, up, act
     b += align((pad_to((int)d, MATRIX_ROW_PADDING) / 32) * 36);  // Q8_1 scratch of the last-token lm_head GEMV
     b += align(mrs_qi_act_bytes(T, (int)std::max(std::max(d, nq), ff))) + align(mrs_gemm_qi_workspace_bytes(T, (int)std::max(d, nq)));  // exact prompt path: Q8_K operands of T rows (f16 quants, scales, run sums) + run sums of split launches
-    if (T > prefill_big_min()) b += align(t * std::max(std::max(d, nq), ff) * 2) + align(mrs_gemm_q_bf16_workspace_bytes(T)) + align(t * ff * 2);  // bf16 activations + split-K partials + act(gate)*up slabs of the fused gate/up GEMM
+    if (T > prefill_big_min) b += align(t * std::max(std::max(d, nq), ff) * 2) + align(mrs_gemm_q_bf16_workspace_bytes(T));  // bf16 activations + split-K partials
     if (c.num_experts > 0) {  // MoE FFN of the prompt: routes = T * top_k rows in expert-sorted order
       const size_t tk = (size_t)std::max(1, (int)c.num_experts_per_tok), r = t * tk, E = (size_t)c.num_experts;
       b += align(r * ff * 4) * 3;                                                    // gate, up, act per route (replace the dense t * ff buffers)
@@ -566,7 +548,7 @@ class Llama {
       b += align(t * (pad_to((int)d, MATRIX_ROW_PADDING) / 32) * 36);                // Q8_1 rows of the normed hidden states
       b += align(r * (pad_to((int)ff, MATRIX_ROW_PADDING) / 32) * 36);               // Q8_1 rows of the routes' activations
       b += align(t * d * 4);                                                         // sum of the weighted expert outputs
-      if (T > prefill_big_min()) b += align(t * d * 2) + align(r * ff * 2);         // bf16 slabs of the normed tokens and of the routes' activations
+      if (T > prefill_big_min) b += align(t * d * 2) + align(r * ff * 2);         // bf16 slabs of the normed tokens and of the routes' activations
       b += align(r * 4) + align(r * d * 4) + align(mrs_qi_act_bytes((int)r, (int)d)) + align(mrs_qi_act_bytes((int)r, (int)ff));  // exact path: inverse route table, per-route down outputs, gathered / per-route operand rows
     }
     return b + 4096;
@@ -595,9 +577,8 @@ class Llama {
     if (mrs_moe_router_topk(xn, bl.router, T, E, d, tk, 1, m.ids, m.w, nullptr, s)) return fail("moe router refused (experts %d, top-k %d)", E, tk);
     launch_moe_dispatch(m.ids, m.bounds, m.sorted, nullptr, routes, E, tk, m.counts, m.cursors, s);
     // long prompts: the grouped GEMMs on the matrix cores (block dequant -> bf16 MFMA, the dense prompt GEMM's arithmetic) over the same dispatch
-    // tables -- every expert's weights are decoded once per 256 of ITS routes.  MRS_MOE_PREFILL_MFMA=0 keeps the int8-dot grouped GEMV route.
-    static const bool mfma_on = [] { const char *e = getenv("MRS_MOE_PREFILL_MFMA"); return !e || atoi(e) != 0; }();
-    if (mfma_on && m.xb && m.yb && d % 64 == 0 && ff % 64 == 0 && bl.up_exps.dtype == bl.gate_exps.dtype) {
+    // tables -- every expert's weights are decoded once per 256 of ITS routes.  Short prompts and other shapes take the int8-dot grouped GEMV route below.
+    if (m.xb && m.yb && d % 64 == 0 && ff % 64 == 0 && bl.up_exps.dtype == bl.gate_exps.dtype) {
       int rc = mrs_convert_f32_bf16_slabs(xn, d, T, d, m.xb, s);
       if (!rc) rc = mrs_moe_gemm_q_bf16(bl.gate_exps.data, bl.gate_exps.dtype, ff, d, E, m.xb, T, m.bounds, m.sorted, tk, 1, nullptr, m.g, ff, routes, s);
       if (!rc) rc = mrs_moe_gemm_q_bf16(bl.up_exps.data, bl.up_exps.dtype, ff, d, E, m.xb, T, m.bounds, m.sorted, tk, 1, nullptr, m.u, ff, routes, s);
@@ -771,14 +752,13 @@ class Llama {
       moe.y_in = take(t * (pad_to(d, MATRIX_ROW_PADDING) / 32) * 36);
       moe.y_act = take(r * (pad_to(ff, MATRIX_ROW_PADDING) / 32) * 36);
       moe.sum = (float *)take(t * d * 4);
-      if (T > prefill_big_min()) { moe.xb = take(t * d * 2); moe.yb = take(r * ff * 2); }
+      if (T > prefill_big_min) { moe.xb = take(t * d * 2); moe.yb = take(r * ff * 2); }
     }
     const int64_t st = (int64_t)(intptr_t)s;
-    // T > 128: the 256-row-tile kernel over bf16 activations (converted once per GEMM group), split-K partials in `part`
-    const bool big = T > prefill_big_min() && !getenv("MRS_PREFILL_SMALL_TILES");
+    // T > prefill_big_min: the 256-row-tile kernel over bf16 activations (converted once per GEMM group), split-K partials in `part`
+    const bool big = T > prefill_big_min;
     const size_t part_bytes = big ? mrs_gemm_q_bf16_workspace_bytes(T) : 0;
     void *xb = big ? take(t * std::max(std::max(d, nq), ff) * 2) : nullptr, *part = big ? take(part_bytes) : nullptr;
-    void *xg = big ? take(t * ff * 2) : nullptr;  // output slabs of the fused gate / up GEMM (it reads xb while it writes)
     const float *xb_src = nullptr;    // which f32 buffer xb currently mirrors (within one GEMM group)
     const float *xb_ready = nullptr;  // set by a producer that wrote the slabs of that (never materialised) f32 buffer directly
     auto to_bf16 = [&](const float *x, int K) -> int {
@@ -923,20 +903,9 @@ class Llama {
       }
       if (big) { if (mrs_rms_norm_bf16_slabs(h, bl.post_attention_layernorm, T, d, cfg.rms_eps, xb, s)) return -1; xb_ready = xn; }
       else mrs_rms_norm_f32(h, bl.post_attention_layernorm, xn, T, d, cfg.rms_eps, st);
-      // gate / up / SiLU*up in ONE launch (act(gate) * up leaves the epilogue as the down GEMM's bf16 slabs): bit-identical, but measured 1.5-2.5 % SLOWER per
-      // prompt on the MI355X than two GEMM segments + the 12.7 us GLU pass (TTFT 14.15 vs 13.82 ms at 512 tokens, 47.5 vs 46.9 ms at 2048: the epilogue's expf and
-      // 2-byte half-line stores sit in the un-overlapped tail of every workgroup) -> opt-in (MRS_PREFILL_FUSED_GLU=1)
-      static const bool glu_fused = [] { const char *e = getenv("MRS_PREFILL_FUSED_GLU"); return e && atoi(e) != 0; }();
-      const QTensor *qg = bl.gate_proj->get_qtensor(), *qu = bl.up_proj->get_qtensor(), *qd = bl.down_proj->get_qtensor();
-      if (big && glu_fused && ff % 64 == 0 && qg->dtype == qu->dtype && xb_ready == xn &&
-          mrs_gemm_q_bf16_glu(qg->data, qu->data, qg->dtype, ff, d, xb, T, 0, xg, s) == 0) {
-        xb_ready = nullptr; xb_src = nullptr;
-        float *dst = cfg.world_size > 1 ? xn : h;
-        if (mrs_gemm_q_bf16_multi(1, &qd->data, &d, &dst, &d, qd->dtype, ff, xg, T, cfg.world_size > 1 ? 0 : 1, part, part_bytes, s))
-          return fail("prefill: no GEMM for ggml dtype %d (K=%d)", qd->dtype, ff);
-        if (cfg.world_size > 1 && (all_reduce(xn, t * d, s) || mrs_vec_add_f32(h, xn, t * d, s))) return -1;
-        continue;
-      }
+      // two GEMM segments + the 12.7 us GLU pass: the one-launch gate / up / SiLU*up GEMM (mrs_gemm_q_bf16_glu) is bit-identical but was measured 1.5-2.5 % SLOWER
+      // per prompt on the MI355X (TTFT 14.15 vs 13.82 ms at 512 tokens, 47.5 vs 46.9 ms at 2048: the epilogue's expf and 2-byte half-line stores sit in the
+      // un-overlapped tail of every workgroup)
       if (gemm_multi({bl.gate_proj.get(), bl.up_proj.get()}, xn, d, {g, u}, {ff, ff})) return -1;
       if (big && ff % 64 == 0) { if (mrs_glu_bf16_slabs(g, u, ff, T, ff, 0, xb, s)) return -1; xb_ready = act; }
       else fused_glu_f32(g, u, act, (uint32_t)T, (uint32_t)ff, (uint32_t)ff, (uint32_t)ff, 0, s);
@@ -972,8 +941,7 @@ class Llama {
   int forward_logits(int b, hipStream_t s) const {
     if (check_ready(b)) return -1;
     // sliding-window attention (Mistral) exists in the decode engine's split attention and in the MFMA prefill only: every other path would silently attend everything
-    if (cfg.sliding_window > 0 && (cfg.use_fused != 2 || !attn2))
-      return fail("sliding_window %d needs the decode engine with its default attention (use_fused = 2, MRS_DEC_ATTN2 / MRS_DEC_FUSED_ATTN / MRS_DEC_PERSIST unset)", cfg.sliding_window);
+    if (cfg.sliding_window > 0 && cfg.use_fused != 2) return fail("sliding_window %d needs the decode engine (use_fused = 2)", cfg.sliding_window);
     if (cfg.use_fused == 2) {  // the engine never falls back silently: its arithmetic (Q8_K activations) differs from the Q8_1 paths
       if (!engine_ok()) return fail("decode engine: needs interleaved RoPE, head_dim 128, block 32, q4_k/q5_k/q6_k/q8_0 linears and a decode-layout copy of every linear");
       return forward_engine(b, s);
@@ -1004,7 +972,6 @@ class Llama {
   int decode_step_chained(int b, hipStream_t s) const {
     if (check_ready(b)) return -1;
     if (!chained_ok(b)) return fail("chained decode step: needs the decode engine at batch 1");
-    if (cfg.sliding_window > 0 && !attn2) return fail("sliding_window %d needs the decode engine with its default attention", cfg.sliding_window);
     if (forward_engine(b, s, true)) return -1;
     const QTensor *e = wte->get_qtensor();
     if (mrs_sample_advance_embed(bufs.input_ids, bufs.tokens_out, bufs.tokens_out_stride, bufs.step_counter, bufs.positions, bufs.context_lens, bufs.slot_mapping,

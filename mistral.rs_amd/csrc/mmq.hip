@@ -630,25 +630,17 @@ __global__ void __launch_bounds__(64 * NW, NW == 4 ? 2 : 3) mmq_mfma_b32_kernel(
 
 template <int TYPE> constexpr bool mmq_is_b32() { return TYPE == T_Q8_0 || TYPE == T_Q4_0 || TYPE == T_Q4_1 || TYPE == T_Q5_0 || TYPE == T_Q5_1; }
 template <int TYPE> constexpr bool mmq_has_mfma() { return TYPE == T_Q4_K || TYPE == T_Q5_K || TYPE == T_Q6_K || TYPE == T_Q3_K || TYPE == T_Q2_K || mmq_is_b32<TYPE>(); }
-// prompt-sized launches of the two DS4 K-quants go to the matrix cores (MRS_MMQ_MFMA=0: keep the v_dot4 kernel, for A/B measurements)
-static int g_mmq_small_below = -1;  // < 0: not set yet (MRS_MMQ_SMALL_TILES_BELOW, default 384 = 1.5 workgroups of 128 x 128 per CU)
-static int mmq_small_tiles_below() {
-  if (g_mmq_small_below < 0) { const char *e = getenv("MRS_MMQ_SMALL_TILES_BELOW"); g_mmq_small_below = e ? atoi(e) : 384; }
-  return g_mmq_small_below;
-}
-static bool mmq_mfma_wanted() {
-  static const bool on = [] { const char *e = getenv("MRS_MMQ_MFMA"); return !e || atoi(e) != 0; }();
-  return on;
-}
+// prompt-sized launches of the two DS4 K-quants go to the matrix cores
+static int g_mmq_small_below = 384;  // 1.5 workgroups of 128 x 128 per CU (mrs_mmq_set_small_tiles_below overrides)
 
 template <int TYPE, class OUT> static void launch_mmq_t(const MmqArgs &a, int64_t channels, int64_t ncols_max, void *stream) {
   constexpr int NC = 8;
   if (a.nrows_x <= 0 || ncols_max <= 0 || channels <= 0) return;
   if constexpr (mmq_has_mfma<TYPE>()) {
-    if (mmq_mfma_wanted() && ncols_max >= 48 && a.nrows_x >= 32 && a.ncols_x % (mmq_is_b32<TYPE>() ? 128 : 256) == 0) {
+    if (ncols_max >= 48 && a.nrows_x >= 32 && a.ncols_x % (mmq_is_b32<TYPE>() ? 128 : 256) == 0) {
       // 128 x 128 tiles when they give every CU its two workgroups, 64 x 64 tiles otherwise (a 4096-row tensor at 512 columns: 128 -> 512 workgroups)
       const int64_t big = ((a.nrows_x + 127) / 128) * ((ncols_max + 127) / 128) * channels;
-      if (big >= mmq_small_tiles_below()) {
+      if (big >= g_mmq_small_below) {
         const dim3 grid((unsigned)((a.nrows_x + 127) / 128), (unsigned)((ncols_max + 127) / 128), (unsigned)channels);
         if constexpr (TYPE == T_Q6_K || TYPE == T_Q3_K || TYPE == T_Q2_K) hipLaunchKernelGGL((mmq_mfma_k16_kernel<TYPE, OUT, 4, 4>), grid, dim3(256), 0, (hipStream_t)stream, a);
         else if constexpr (mmq_is_b32<TYPE>()) hipLaunchKernelGGL((mmq_mfma_b32_kernel<TYPE, OUT, 4, 4>), grid, dim3(256), 0, (hipStream_t)stream, a);

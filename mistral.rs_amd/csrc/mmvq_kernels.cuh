@@ -220,13 +220,9 @@ template <int TYPE, int NC> inline void moe_grouped_launch(const MoeGroupedArgs 
 }
 
 // rows per wave so that the grid is ~16 waves on each of the 256 CUs (all resident at once: no tail wave)
-inline int mmvq_target_waves() {
-  static int v = 0;
-  if (!v) { const char *e = getenv("MRS_MMVQ_WAVES"); v = e ? atoi(e) : 4096; if (v < 256) v = 256; }
-  return v;
-}
+constexpr int MMVQ_TARGET_WAVES = 4096;
 inline int mmvq_rows_per_wave(int total_rows, bool want_even) {
-  const int t = mmvq_target_waves();
+  const int t = MMVQ_TARGET_WAVES;
   int r = (total_rows + t - 1) / t;
   if (r < 1) r = 1;
   if (want_even && (r & 1)) ++r;  // paired-row formats walk two rows per step
