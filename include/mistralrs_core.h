@@ -42,7 +42,7 @@ void moe_router_topk_bf16(const void *logits, float *weights, uint32_t *ids, con
                           float clamp_max, float norm_min, float output_scale, int64_t stream);
 
 /* Sampling: top-k of one f32 logits row over a large vocabulary + the pieces of the full-softmax normaliser (Sampler::sample_topk_on_device, sampler.rs:1171-1260;
- * top-p / min-p / the draw stay on the host).  The caller owns every buffer: block_values / block_indices [nrows][nblocks][k], block_maxes / block_sums
+ * with top-k set, top-p / min-p / the draw stay on the host; the draw WITHOUT top-k runs on the device, see categorical_large_f32_packed_batched below).  The caller owns every buffer: block_values / block_indices [nrows][nblocks][k], block_maxes / block_sums
  * [nrows][nblocks] (workspace, nblocks = ceil(ncols / chunk_size)), packed_out [nrows][2k + 2] = k values, k indices as f32, denom, max(x / T).
  * Order: value descending, index ascending on ties; NaN and -inf are never selected, missing entries are (-inf, 0).  1 <= k <= 128, chunk_size <= 4096 (the
  * reference's host wrapper passes 2048).  replaces mistralrs-core/src/cuda/sort.cu:1502-1823,2146-2206 ; ffi.rs:583-624 ; caller ops.rs:691-1000 */
@@ -60,6 +60,21 @@ void top1_large_f32_packed(const float *input, float *block_values, uint32_t *bl
                            int nblocks, int64_t stream);
 void top1_large_f32_packed_batched(const float *input, float *block_values, uint32_t *block_indices, float *packed_out, uint32_t *token_ids_out, int nrows, int ncols,
                                    int chunk_size, int nblocks, int64_t stream);
+
+/* Temperature sampling over the whole vocabulary (top_k unset, top_p / min_p inactive): one draw per row from softmax(x * inv_temperature) at the caller's uniform.
+ * The caller owns every buffer: block_values / block_sums [nrows][nblocks] (workspace), packed_out [nrows][2] = (token id as f32, log-probability of that token
+ * under the full softmax at that temperature).  block_values[row][chunk] = the chunk's largest raw logit (NaN if the chunk holds a NaN, -inf if nothing is above
+ * -inf); block_sums[row][chunk] = sum over the chunk of expf(x * invT - block_value * invT) (NaN if the chunk holds a NaN, 0 when the chunk maximum is -inf).
+ * Per row: gmax = max_b(block_values) * invT; denom = sum_b block_sums[b] * expf(block_values[b] * invT - gmax), added in chunk order;
+ * target = min(u * denom, nextafterf(denom, -inf)); the chunk is the first whose running mass exceeds target; inside it the token is the LOWEST index with weight > 0
+ * whose inclusive cumulative weight exceeds the remaining target (if rounding leaves none: the chunk's last index with weight > 0).  A token of weight 0 (a -inf logit,
+ * underflow) is never returned.  The row reports (NaN, NaN) when invT is not finite or <= 0, u is outside [0, 1) or not finite, gmax is not finite (a NaN anywhere in
+ * the row, a +inf logit, a row of -inf), or denom is not finite or <= 0; other rows of the launch are unaffected.  Returns without launching when nrows < 1, ncols < 1,
+ * chunk_size < 1 or > 4096, or nblocks * chunk_size < ncols; any chunk_size in 1..4096 is served (the reference's host wrapper passes 2048).  The order of the f32
+ * additions inside a chunk is this library's (per-thread runs + a lane scan), not the reference's tree: tokens agree wherever u is not within f32 rounding of a boundary.
+ * replaces mistralrs-core/src/cuda/sort.cu:1825-2069,2240-2257 ; ffi.rs:666 ; callers ops.rs:1347-1500, pipeline/sampling.rs:999-1018, sampler.rs:649-652,744-764 */
+void categorical_large_f32_packed_batched(const float *input, const float *inv_temperatures, const float *uniforms, float *block_values, float *block_sums,
+                                          float *packed_out, int nrows, int ncols, int chunk_size, int nblocks, int64_t stream);
 
 /* Sampler pre-processing: dst [n] = x [n] (f32), then for the n_tokens listed token ids (ids >= n ignored): penalties -- skipped where count <= 0;
  * v -= count * frequency_penalty + presence_penalty; if repetition_penalty != 1: v = v > 0 ? v / rp : v * rp -- or additive biases.

@@ -1,5 +1,7 @@
 // sampling.hip -- libmistralrscuda, sampling subset: top-k of one logits row over a 100k+ vocabulary + the pieces of the full-softmax normaliser the host
-// sampler needs (Sampler::sample_topk_on_device, mistralrs-core/src/sampler.rs:1171-1260: top-p / min-p / the multinomial draw stay on the host).
+// sampler needs (Sampler::sample_topk_on_device, mistralrs-core/src/sampler.rs:1171-1260: with top-k set, top-p / min-p / the multinomial draw stay on the host);
+// the greedy arg-max; and the categorical draw over the WHOLE row (temperature only, no top-k: the draw itself runs on the device, see the section further down).
+//   categorical_large_f32_packed_batched                                      sort.cu:1825-2069,2240-2257 ; ffi.rs:666 ; caller ops.rs:1347-1500 (temperature sampling)
 //   top1_large_f32_packed, top1_large_f32_packed_batched                     sort.cu:1825-1912,2071-2143,2207-2238 ; ffi.rs:643-665 ; caller ops.rs:1232-2000 (greedy)
 //   topk_large_f32, topk_large_f32_packed, topk_large_f32_packed_batched      mistralrs-core/src/cuda/sort.cu:1502-1823,2146-2206 ; ffi.rs:583-624 ;
 //                                                                              caller ops.rs:691-828 (cuda_topk_logits_f32_packed)
@@ -382,6 +384,216 @@ static void run_top1(const float *input, float *block_values, uint32_t *block_in
   }
 }
 
+// ---------------------------------------------------------------- temperature sampling over the whole row: categorical_large_f32_packed_batched
+// (the reference's symbol: ffi.rs:666, sort.cu:1825-2069, 2240-2257; callers ops.rs:1347-1500, sampler.rs:649-652, 744-764).  One draw per row from softmax(x * invT) by
+// inverting the cumulative distribution at the caller's uniform -- no top-k cut, nothing leaves the device but (token, logprob).
+// stage 1, one workgroup per chunk: block_values = the chunk's largest raw logit (NaN if it holds one, -inf if nothing is above -inf), block_sums = the chunk's
+//   sum of expf(x * invT - block_value * invT) -- the chunk is read ONCE into registers, max and sum both come from them; the sum keeps topk stage 1's association.
+// stage 2, one workgroup per row: gmax = max_b block_values * invT; the chunk masses block_sums[b] * expf(block_values[b] * invT - gmax) computed once by all
+//   threads, added in chunk order by thread 0 (running sums kept: the chunk that holds the target is a binary search over them); then the selected chunk, each thread
+//   owning a CONTIGUOUS run of ceil(chunk_size / 256) tokens: thread-local running sums, an inclusive scan of the thread totals across the lanes (DPP row rotates +
+//   v_readlane), the four wave totals through LDS with one barrier, and every thread tests its own tokens only.  Any chunk_size in 1..4096.
+struct CatArgs {
+  const float *input, *inv_temperatures, *uniforms;
+  float *block_values, *block_sums, *packed_out;
+  int ncols, chunk_size, nblocks;
+};
+constexpr int CAT_MAXB = 4096;  // running chunk masses kept in LDS; the chunks beyond (vocabularies > 8 M tokens at chunk_size 2048) are recomputed by the walk
+
+__device__ __forceinline__ bool finite_f32(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
+
+__global__ void __launch_bounds__(NT) cat_stage1_kernel(CatArgs a) {
+  __shared__ float s_warp_sums[32];
+  __shared__ float s_wmax[4];
+  __shared__ int s_wnan[4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, chunk = blockIdx.x;
+  const size_t row = blockIdx.y;
+  const float *input = a.input + row * (size_t)a.ncols;
+  const float inv_t = a.inv_temperatures[row];
+  const long long start = (long long)chunk * a.chunk_size, left = (long long)a.ncols - start;
+  const int width = left <= 0 ? 0 : (left < a.chunk_size ? (int)left : a.chunk_size);
+  // the chunk in registers, thread-strided (local = tid + 256 j) as in topk stage 1: the partial sums below are the same partial sums
+  float v[MAXV];
+  float m = -INFINITY;
+  bool nan = false;
+#pragma unroll
+  for (int j = 0; j < MAXV; ++j) {
+    const int local = tid + j * NT;
+    v[j] = local < width ? input[start + local] : -INFINITY;
+    if (v[j] != v[j]) nan = true;
+    else m = fmaxf(m, v[j]);
+  }
+  m = wave_max(m);
+  const bool wave_nan = __ballot(nan) != 0ull;
+  if (lane == 0) { s_wmax[wave] = m; s_wnan[wave] = wave_nan ? 1 : 0; }
+  __syncthreads();
+  const bool any_nan = (s_wnan[0] | s_wnan[1] | s_wnan[2] | s_wnan[3]) != 0;
+  const float block_value = any_nan ? NAN : fmaxf(fmaxf(s_wmax[0], s_wmax[1]), fmaxf(s_wmax[2], s_wmax[3]));
+  const float block_max = block_value * inv_t;
+  float local_sum = 0.0f;
+#pragma unroll
+  for (int j = 0; j < MAXV; ++j) {
+    const int local = tid + j * NT;
+    if (local < width) {
+      const float c = v[j];
+      if (c != c) local_sum = NAN;
+      else if (block_value != -INFINITY) local_sum += expf(c * inv_t - block_max);
+    }
+  }
+  const float block_sum = block_sum_ref_order(local_sum, s_warp_sums);
+  if (tid == 0) {
+    a.block_values[row * a.nblocks + chunk] = block_value;
+    a.block_sums[row * a.nblocks + chunk] = block_sum;
+  }
+}
+
+// inclusive / exclusive prefix sums of one value per lane over the wave, and the wave's total: a Hillis-Steele scan inside each row of 16 lanes on DPP row
+// rotates (a lane that would wrap around adds nothing), then the three row totals through v_readlane.  excl(l) == incl(l - 1) bit for bit.
+template <int N> __device__ __forceinline__ float row_ror_f32(float v) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x120 + N, 0xf, 0xf, false));
+}
+__device__ __forceinline__ void wave_scan_f32(float v, float &excl, float &total) {
+  const int lane = threadIdx.x & 63, i = lane & 15, r = lane >> 4;
+  float t;
+  t = row_ror_f32<1>(v); if (i >= 1) v += t;
+  t = row_ror_f32<2>(v); if (i >= 2) v += t;
+  t = row_ror_f32<4>(v); if (i >= 4) v += t;
+  t = row_ror_f32<8>(v); if (i >= 8) v += t;
+  t = row_ror_f32<1>(v);
+  const float e = i >= 1 ? t : 0.0f;  // exclusive inside the row
+  const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 15)), r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 31));
+  const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 47)), r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
+  const float o1 = r0, o2 = r0 + r1, o3 = o2 + r2;
+  const float off = r == 0 ? 0.0f : (r == 1 ? o1 : (r == 2 ? o2 : o3));
+  excl = r == 0 ? e : off + e;
+  total = o3 + r3;
+}
+
+__global__ void __launch_bounds__(NT) cat_stage2_kernel(CatArgs a) {
+  __shared__ float s_cum[CAT_MAXB];  // chunk masses, then their running sums
+  __shared__ float s_wmax[4], s_wtot[4], s_wlast[4];
+  __shared__ int s_wnan[4], s_wfirst[4];
+  __shared__ float s_denom, s_target;
+  __shared__ int s_sel;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nb = a.nblocks;
+  const size_t row = blockIdx.x;
+  const float *input = a.input + row * (size_t)a.ncols;
+  const float *bv = a.block_values + row * (size_t)nb, *bs = a.block_sums + row * (size_t)nb;
+  float *packed = a.packed_out + row * 2;
+  const float inv_t = a.inv_temperatures[row];
+  // ---- gmax (fmaxf drops a NaN: it is carried as a flag)
+  float m = -INFINITY;
+  bool nan = false;
+  for (int b = tid; b < nb; b += NT) {
+    const float c = bv[b];
+    if (c != c) nan = true;
+    else m = fmaxf(m, c);
+  }
+  m = wave_max(m);
+  const bool wave_nan = __ballot(nan) != 0ull;
+  if (lane == 0) { s_wmax[wave] = m; s_wnan[wave] = wave_nan ? 1 : 0; }
+  __syncthreads();
+  const bool any_nan = (s_wnan[0] | s_wnan[1] | s_wnan[2] | s_wnan[3]) != 0;
+  const float gmax = any_nan ? NAN : fmaxf(fmaxf(s_wmax[0], s_wmax[1]), fmaxf(s_wmax[2], s_wmax[3])) * inv_t;
+  // ---- the chunk masses, once
+  auto mass = [&](int b) { return bs[b] * expf(bv[b] * inv_t - gmax); };
+  for (int b = tid; b < nb && b < CAT_MAXB; b += NT) s_cum[b] = mass(b);
+  __syncthreads();
+  // ---- thread 0: denom in chunk order, the target, the chunk that holds it
+  if (tid == 0) {
+    float cum = 0.0f;
+    for (int b = 0; b < nb; ++b) {
+      cum += b < CAT_MAXB ? s_cum[b] : mass(b);
+      if (b < CAT_MAXB) s_cum[b] = cum;
+    }
+    const float denom = cum, u = a.uniforms[row];
+    int sel = -1;
+    float target = NAN;
+    if (inv_t > 0.0f && finite_f32(inv_t) && u >= 0.0f && u < 1.0f && finite_f32(gmax) && denom > 0.0f && finite_f32(denom)) {
+      target = fminf(u * denom, nextafterf(denom, -INFINITY));
+      const int nl = nb < CAT_MAXB ? nb : CAT_MAXB;
+      float before = 0.0f;
+      if (target < s_cum[nl - 1]) {  // the running sums never decrease: the first one above the target by bisection
+        int lo = 0, hi = nl - 1;
+        while (lo < hi) {
+          const int mid = (lo + hi) >> 1;
+          if (target < s_cum[mid]) hi = mid;
+          else lo = mid + 1;
+        }
+        sel = lo;
+        before = lo > 0 ? s_cum[lo - 1] : 0.0f;
+      } else {  // beyond the staged chunks: walk on
+        float c = s_cum[nl - 1];
+        for (int b = nl; b < nb; ++b) {
+          const float next = c + mass(b);
+          if (target < next) { sel = b; before = c; break; }
+          c = next;
+        }
+      }
+      target -= before;
+    }
+    s_sel = sel;
+    s_target = target;
+    s_denom = denom;
+    if (sel < 0) { packed[0] = NAN; packed[1] = NAN; }
+  }
+  __syncthreads();
+  const int sel = s_sel;
+  if (sel < 0) return;
+  const float target = s_target;
+  // ---- the selected chunk: thread t owns the tokens [t * per, t * per + per)
+  const long long start = (long long)sel * a.chunk_size, left = (long long)a.ncols - start;
+  const int width = left < a.chunk_size ? (int)left : a.chunk_size;
+  const int per = (a.chunk_size + NT - 1) / NT, first = tid * per;
+  float w[MAXV], run[MAXV];  // weights, and their running sums inside the thread
+  float acc = 0.0f;
+#pragma unroll
+  for (int j = 0; j < MAXV; ++j) {
+    const int local = first + j;
+    w[j] = (j < per && local < width) ? expf(input[start + local] * inv_t - gmax) : 0.0f;
+    acc += w[j];
+    run[j] = acc;
+  }
+  float excl, wave_total;
+  wave_scan_f32(acc, excl, wave_total);
+  if (lane == 0) s_wtot[wave] = wave_total;
+  __syncthreads();
+  const float t0 = s_wtot[0], t01 = t0 + s_wtot[1], t012 = t01 + s_wtot[2];
+  const float base = wave == 0 ? excl : (wave == 1 ? t0 : (wave == 2 ? t01 : t012)) + excl;
+  // the lowest token with weight > 0 whose inclusive cumulative weight exceeds the target; and the last token with weight > 0, for when rounding leaves none
+  int hit = -1, last = -1;
+#pragma unroll
+  for (int j = MAXV - 1; j >= 0; --j) {
+    if (w[j] > 0.0f) {
+      if (last < 0) last = first + j;
+      if (base + run[j] > target) hit = first + j;
+    }
+  }
+  const unsigned long long hits = __ballot(hit >= 0);  // threads own ascending runs: the lowest lane with a hit holds the wave's lowest token
+  const int first_lane = hits ? __ffsll((long long)hits) - 1 : 0;
+  const int wave_first = __builtin_amdgcn_readlane(hit, first_lane);
+  const float wave_last = wave_max((float)last);  // < 4096: exact in f32
+  if (lane == 0) { s_wfirst[wave] = hits ? wave_first : -1; s_wlast[wave] = wave_last; }
+  __syncthreads();
+  if (tid == 0) {
+    int token = -1;
+    for (int i = 3; i >= 0; --i) if (s_wfirst[i] >= 0) token = s_wfirst[i];
+    if (token < 0) token = (int)fmaxf(fmaxf(s_wlast[0], s_wlast[1]), fmaxf(s_wlast[2], s_wlast[3]));
+    if (token < 0) { packed[0] = NAN; packed[1] = NAN; return; }  // unreachable while the chunk's mass is > 0
+    packed[0] = (float)(start + token);
+    packed[1] = input[start + token] * inv_t - gmax - logf(s_denom);
+  }
+}
+
+static void run_categorical(const float *input, const float *inv_temperatures, const float *uniforms, float *block_values, float *block_sums, float *packed_out, int nrows,
+                            int ncols, int chunk_size, int nblocks, int64_t stream) {
+  if (nrows < 1 || ncols < 1 || chunk_size < 1 || chunk_size > NT * MAXV || (long long)nblocks * chunk_size < ncols) return;
+  hipStream_t s = (hipStream_t)stream;
+  CatArgs a{input, inv_temperatures, uniforms, block_values, block_sums, packed_out, ncols, chunk_size, nblocks};
+  hipLaunchKernelGGL(cat_stage1_kernel, dim3(nblocks, nrows), dim3(NT), 0, s, a);
+  hipLaunchKernelGGL(cat_stage2_kernel, dim3(nrows), dim3(NT), 0, s, a);
+}
+
 // ---------------------------------------------------------------- logits pre-processing of the sampler (sort.cu:8-110; callers sampler.rs:1113-1169)
 // dst = x, then the listed tokens are updated in place: penalties (frequency / presence / repetition, counts from the context) or additive biases.
 __global__ void __launch_bounds__(NT) copy_f32_kernel(const float *__restrict__ x, float *__restrict__ dst, int n) {
@@ -438,6 +650,10 @@ extern "C" void top1_large_f32_packed(const float *input, float *block_values, u
 extern "C" void top1_large_f32_packed_batched(const float *input, float *block_values, uint32_t *block_indices, float *packed_out, uint32_t *token_ids_out, int nrows,
                                               int ncols, int chunk_size, int nblocks, int64_t stream) {
   mrs::sampling::run_top1(input, block_values, block_indices, packed_out, token_ids_out, nrows, ncols, chunk_size, nblocks, true, stream);
+}
+extern "C" void categorical_large_f32_packed_batched(const float *input, const float *inv_temperatures, const float *uniforms, float *block_values, float *block_sums,
+                                                     float *packed_out, int nrows, int ncols, int chunk_size, int nblocks, int64_t stream) {
+  mrs::sampling::run_categorical(input, inv_temperatures, uniforms, block_values, block_sums, packed_out, nrows, ncols, chunk_size, nblocks, stream);
 }
 extern "C" void apply_sparse_penalties_f32(const void *x, void *dst, const uint32_t *token_ids, const float *counts, const int n, const int n_tokens,
                                            const float frequency_penalty, const float presence_penalty, const float repetition_penalty, int64_t stream) {

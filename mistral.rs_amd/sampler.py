@@ -1,9 +1,14 @@
-"""Top-k / top-p / min-p sampling: the role of `Sampler::sample_topk_on_device` (mistralrs-core/src/sampler.rs:1171-1290).
+"""Sampling: the roles of `Sampler::sample_topk_on_device` (mistralrs-core/src/sampler.rs:1171-1290) and of the batched device categorical draw
+(pipeline/sampling.rs:999-1018, sampler.rs:649-652, 744-764).
 
-Device half (csrc/sampling.hip, reference ABI `topk_large_f32_packed[_batched]`, ops.rs:691-1000): the k largest logits of a row in (value descending, index
-ascending) order + the pieces of the full-softmax normaliser, ONE small device -> host copy of `2k + 2` floats per row.  Host half (this file): probabilities of the
-candidates under the FULL softmax, the top-p cut, the min-p cut, the weighted draw.  The reference draws with `rand`'s Isaac64Rng + WeightedIndex; this module draws
-with numpy's Generator from the SAME weights, so the distribution is the reference's and the random stream is not (documented in DESIGN.md)."""
+With top-k set -- device half (csrc/sampling.hip, reference ABI `topk_large_f32_packed[_batched]`, ops.rs:691-1000): the k largest logits of a row in (value
+descending, index ascending) order + the pieces of the full-softmax normaliser, ONE small device -> host copy of `2k + 2` floats per row.  Host half (this file):
+probabilities of the candidates under the FULL softmax, the top-p cut, the min-p cut, the weighted draw.
+Without top-k (temperature only, top-p and min-p inactive) -- the draw itself runs on the device (`categorical_large_f32_packed_batched`, ops.rs:1347-1500): the
+cumulative distribution of softmax(x / T) is inverted at one uniform per row, and 2 floats per row (token, logprob) come back.  `categorical_host` states the same rule in
+numpy f32; it serves logits that live on the CPU.
+The reference draws with `rand`'s Isaac64Rng (+ WeightedIndex for top-k); this module draws with numpy's Generator from the SAME weights -- `uniform_for` for the
+categorical path -- so the distribution is the reference's and the random stream is not (documented in DESIGN.md)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -133,20 +138,107 @@ def sample(packed: np.ndarray, k: int, temperature: float, top_p: float, min_p: 
     return int(ids[j]), float(rep[j])
 
 
+class Categorical:
+    """Workspace + launcher of the device categorical draw over rows of `vocab` f32 logits (cuda_categorical_logits_f32_packed_batched, ops.rs:1347-1500)."""
+
+    def __init__(self, vocab: int, device, max_rows: int = 1):
+        vocab, max_rows = int(vocab), int(max_rows)
+        if vocab <= 0:
+            raise ValueError("categorical: empty logits")
+        if vocab > 2 ** 24:
+            raise ValueError(f"categorical: vocab={vocab} exceeds 2**24 (token ids come back as f32)")  # ops.rs:1387
+        if max_rows < 1 or max_rows > 65535:
+            raise ValueError(f"categorical: max_rows={max_rows} must be in [1, 65535]")
+        self.vocab, self.max_rows, self.device = vocab, max_rows, device
+        self.nblocks = (vocab + CHUNK_SIZE - 1) // CHUNK_SIZE
+        f32 = dict(dtype=torch.float32, device=device)
+        self.block_values = torch.empty(max_rows, self.nblocks, **f32)
+        self.block_sums = torch.empty(max_rows, self.nblocks, **f32)
+        self.packed = torch.empty(max_rows, 2, **f32)
+        self._params = torch.empty(2, max_rows, **f32)  # [0] inverse temperatures, [1] uniforms: one upload
+        vp, i, ll = C.c_void_p, C.c_int, C.c_int64
+        self._many = _lib.sym("core", "categorical_large_f32_packed_batched", [vp, vp, vp, vp, vp, vp, i, i, i, i, ll])
+
+    def __call__(self, logits: torch.Tensor, temperature, uniforms) -> torch.Tensor:
+        """logits f32 [vocab] or [rows, vocab] (contiguous, on the device); temperature: a positive finite float, or one per row; uniforms: one value in [0, 1)
+        per row.  Returns the packed rows [rows, 2] = (token id, logprob) on the device (a view of this object's buffer: consume it before the next call)."""
+        x = logits.reshape(-1, self.vocab) if logits.dim() > 1 else logits.reshape(1, self.vocab)
+        rows = x.shape[0]
+        if x.dtype != torch.float32 or not x.is_contiguous() or rows > self.max_rows:
+            raise ValueError("categorical: logits must be contiguous f32 with at most max_rows rows")
+        temps = np.broadcast_to(np.asarray(temperature, dtype=np.float64), (rows,))
+        if not np.all(np.isfinite(temps) & (temps > 0)):
+            raise ValueError("categorical requires a positive finite temperature")
+        u = np.asarray(uniforms, dtype=np.float32).reshape(-1)
+        if u.shape[0] != rows or not np.all((u >= 0) & (u < 1)):
+            raise ValueError("categorical requires one uniform in [0, 1) per row")
+        params = np.stack([(1.0 / temps).astype(np.float32), u])
+        self._params[:, :rows].copy_(torch.from_numpy(params), non_blocking=False)
+        self._many(x.data_ptr(), self._params[0].data_ptr(), self._params[1].data_ptr(), self.block_values.data_ptr(), self.block_sums.data_ptr(),
+                   self.packed.data_ptr(), rows, self.vocab, CHUNK_SIZE, self.nblocks, torch.cuda.current_stream().cuda_stream)
+        return self.packed[:rows]
+
+
+def categorical_token(packed2):
+    """Sampler::sample_cuda_categorical_row (sampler.rs:744-764): (token, logprob) of one packed pair; the token must be a finite non-negative integer, the logprob finite"""
+    tok, lp = float(packed2[0]), float(packed2[1])
+    if not (np.isfinite(tok) and np.isfinite(lp)) or tok < 0 or tok != np.floor(tok):
+        raise ValueError("invalid batched CUDA categorical output")
+    return int(tok), lp
+
+
+def uniform_for(seed: int, index: int) -> np.float32:
+    """The uniform in [0, 1) that draws token `index` of a request with `seed`: a function of (seed, index) alone, never of the call order -- a preempted and
+    recomputed sequence redraws the same tokens.  The reference's distribution, not its Isaac64 stream."""
+    return np.float32(np.random.default_rng((int(seed), int(index))).random(dtype=np.float32))
+
+
+def categorical_host(logits_row, inv_temperature, uniform):
+    """The contract of `categorical_large_f32_packed_batched` for one row in numpy f32 (one chunk, additions in index order): (token, logprob).  Raises like
+    `categorical_token` where the device reports (NaN, NaN)."""
+    x, inv_t, u = np.asarray(logits_row, dtype=np.float32).reshape(-1), np.float32(inv_temperature), np.float32(uniform)
+    with np.errstate(over="ignore", invalid="ignore"):
+        gmax = np.float32(x.max() * inv_t) if x.size else np.float32(np.nan)
+        ok = np.isfinite(inv_t) and inv_t > 0 and np.isfinite(u) and 0 <= u < 1 and np.isfinite(gmax)
+        if ok:
+            w = np.exp((x * inv_t - gmax).astype(np.float32), dtype=np.float32)
+            cum = np.cumsum(w, dtype=np.float32)  # sequential f32 additions
+            denom = cum[-1]
+            ok = np.isfinite(denom) and denom > 0
+    if not ok:
+        raise ValueError("invalid batched CUDA categorical output")
+    target = min(np.float32(u * denom), np.nextafter(denom, np.float32(-np.inf)))
+    hit = np.nonzero((w > 0) & (cum > target))[0]
+    tok = int(hit[0]) if hit.size else int(np.nonzero(w > 0)[0][-1])
+    return tok, float(np.float32(np.float32(x[tok] * inv_t - gmax) - np.log(denom, dtype=np.float32)))
+
+
 def generate(model, prompt, max_new_tokens: int, top_k: int, temperature: float = 1.0, top_p: float = 1.0, min_p: float = 0.0, seed: int = 0):
-    """Sampled decoding on a `Llama` runner (the loop of `Sampler::sample` with top_k set, sampler.rs:1262-1290): prefill, then per token one decode step, the device
-    top-k over the logits row, `2k + 2` floats to the host, the top-p / min-p cuts and the draw there.  top_k == 1 takes the arg-max through the top-1 kernels, no temperature, probability 1
-    (sample_cuda_top1_row).  Returns (tokens, reporting probabilities)."""
+    """Sampled decoding on a `Llama` runner (the loop of `Sampler::sample`, sampler.rs:1262-1290): prefill, then per token one decode step and
+      top_k >= 2: the device top-k over the logits row, `2k + 2` floats to the host, the top-p / min-p cuts and the draw there;
+      top_k == 1: the arg-max through the top-1 kernels, no temperature, probability 1 (sample_cuda_top1_row);
+      top_k <= 0 or None (top_p and min_p inactive): the device categorical draw over the whole row at `uniform_for(seed, i)` -- one launch pair, 2 floats to the host,
+                 probability exp(logprob).  With an active top_p or min_p this raises: the reference falls back to its CPU sampler there, which is not mirrored.
+    Returns (tokens, reporting probabilities)."""
+    vocab = int(model.cfg.vocab_size)
+    if top_k is None or int(top_k) <= 0:
+        if 0.0 < top_p < 1.0 or 0.0 < min_p < 1.0:
+            raise ValueError("sampling with top_p / min_p needs top_k >= 1 (the device categorical draw takes the whole row)")
+        k, t1, tk, cat = 0, None, None, Categorical(vocab, model.device)
+    else:
+        k = min(int(top_k), vocab)
+        t1 = Top1(vocab, model.device) if k == 1 else None
+        tk = None if k == 1 else TopK(vocab, top_k, model.device)
     rng = np.random.default_rng(seed)
-    k = min(int(top_k), int(model.cfg.vocab_size))
-    t1 = Top1(model.cfg.vocab_size, model.device) if k == 1 else None
-    tk = None if k == 1 else TopK(model.cfg.vocab_size, top_k, model.device)
     logits = model.prefill(list(prompt), 0).float().reshape(1, -1)  # sequence 0: the decode steps below run batch row 0
     toks, probs = [], []
     for i in range(max_new_tokens):
         if hasattr(model, "p2p_sync_error") and model.p2p_sync_error():  # tensor parallel: a timed-out peer-mailbox sum is NaN -- never hand out a token from it
             raise RuntimeError("p2p all-reduce timed out: the route has been dropped on every rank (RCCL from now on); re-run the request")
-        if k == 1:  # sample_cuda_top1_row (sampler.rs:767-781): the arg-max, no temperature, logprob 0 (probability 1)
+        if k == 0:
+            tok, lp = categorical_token(cat(logits.contiguous(), temperature, [uniform_for(seed, i)]).cpu().numpy()[0])
+            p = min(1.0, float(np.exp(lp)))
+        elif k == 1:  # sample_cuda_top1_row (sampler.rs:767-781): the arg-max, no temperature, logprob 0 (probability 1)
             tok, p = top1_token(t1(logits.contiguous()).cpu().numpy()[0]), 1.0
         else:
             packed = tk(logits.contiguous(), temperature).cpu().numpy()[0]

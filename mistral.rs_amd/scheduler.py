@@ -21,6 +21,8 @@ from collections import deque
 from dataclasses import dataclass, field
 from typing import List, Optional
 
+import numpy as np
+
 from .kv_cache_manager import KVCacheManager, compute_block_hashes
 
 WAITING_TIMEOUT = 64  # scheduler.rs:48
@@ -41,6 +43,9 @@ class Sequence:
     error: Optional[str] = None
     generated: List[int] = field(default_factory=list)
     last_logits: object = None
+    temperature: Optional[float] = None   # None: greedy (arg-max); else the categorical draw over the whole row at this temperature
+    seed: int = 0                         # token j is drawn at sampler.uniform_for(seed, j): a recomputed sequence redraws the same tokens
+    logprobs: List[float] = field(default_factory=list)  # one entry per SAMPLED token (greedy tokens add none)
 
     def __post_init__(self):
         if not self.prompt_len:
@@ -283,7 +288,7 @@ class PagedAttentionScheduler:
 
 
 class PagedEngine:
-    """Drives `mistralrs_amd.llama.Llama` with the scheduler: greedy decoding of many sequences through the batch <= 8 decode engine, prompts in chunks of
+    """Drives `mistralrs_amd.llama.Llama` with the scheduler: greedy (or, per sequence, temperature-sampled) decoding of many sequences through the batch <= 8 decode engine, prompts in chunks of
     `prompt_chunk_size` tokens through the same kernels (so a preempted and recomputed sequence reproduces its logits bit for bit), block tables and slot
     mappings from the KV cache manager (pipeline/inputs_processor.rs:900-922)."""
 
@@ -291,18 +296,47 @@ class PagedEngine:
         self.m, self.s = model, scheduler
         self.cfg = model.cfg
         self.steps = {"prompt": 0, "completion": 0, "preemptions": 0}
+        self._cat = None  # sampler.Categorical, made at the first sampled token
 
     def _table(self, seq: Sequence):
         import torch
         return torch.tensor(self.s.kv.get_block_table(seq.id, self.cfg.max_blocks_per_seq), dtype=self.m.block_tables.dtype, device=self.m.device)
 
-    def _finish_token(self, seq: Sequence, logits) -> None:
-        tok = int(logits.argmax())
+    def _finish_token(self, seq: Sequence, logits, tok: Optional[int] = None) -> None:
+        tok = int(logits.argmax()) if tok is None else tok
         seq.last_logits = logits.clone()
         seq.tokens.append(tok)
         seq.generated.append(tok)
         if len(seq.generated) >= seq.max_new_tokens or len(seq.tokens) >= self.cfg.max_context_len:
             seq.state = DONE
+
+    def _finish_tokens(self, seqs: List[Sequence], logits) -> None:
+        """The next token of every row of one launch (`logits[i]` belongs to `seqs[i]`): rows with a temperature are drawn TOGETHER -- one categorical launch pair over
+        their logits with per-row inverse temperature and uniform, one copy of 2 floats per row; greedy rows keep the arg-max.  A (NaN, NaN) pair raises.
+        Tensor parallel: every rank holds the same logits after the all-reduce and derives the same uniforms from (seed, position), so every rank draws the
+        same token without any further communication."""
+        from . import sampler
+        sampled = [i for i, s in enumerate(seqs) if s.temperature is not None]
+        drawn = {}
+        if sampled:
+            us = [sampler.uniform_for(seqs[i].seed, len(seqs[i].generated)) for i in sampled]
+            if self.m.device.type == "cpu":  # host runners: the same rule in numpy
+                for i, u in zip(sampled, us):
+                    drawn[i] = sampler.categorical_host(logits[i].float().numpy(), np.float32(1.0 / seqs[i].temperature), u)
+            else:
+                import torch
+                x = logits[sampled[0]: sampled[0] + 1] if len(sampled) == 1 else logits[torch.tensor(sampled, device=logits.device)]
+                if self._cat is None:
+                    self._cat = sampler.Categorical(self.cfg.vocab_size, self.m.device, max_rows=max(8, self.cfg.max_batch))
+                packed = self._cat(x.float().contiguous(), [seqs[i].temperature for i in sampled], us).cpu().numpy()
+                for r, i in enumerate(sampled):
+                    drawn[i] = sampler.categorical_token(packed[r])
+        for i, seq in enumerate(seqs):
+            if i in drawn:
+                seq.logprobs.append(drawn[i][1])
+                self._finish_token(seq, logits[i], drawn[i][0])
+            else:
+                self._finish_token(seq, logits[i])
 
     def _p2p_guard(self) -> None:
         """Tensor parallel: before tokens are handed out, the per-rank error word of the peer-mailbox all-reduce is MAX-reduced over the ranks (Llama.p2p_sync_error);
@@ -330,7 +364,7 @@ class PagedEngine:
                 seq.num_computed_tokens = b
                 if b == len(seq):  # the prompt's last token produced the first new token (llama.rs:514-517: logits of the last position only)
                     seq.state = RUNNING_COMPLETION
-                    self._finish_token(seq, last)
+                    self._finish_tokens([seq], last.reshape(1, -1))
         elif out.kind == "completion":
             self.steps["completion"] += 1
             # every scheduled row decodes in THIS step (the scheduler has reserved its slot and counted the step): launches of up to max_batch rows
@@ -341,9 +375,9 @@ class PagedEngine:
                 self.m.set_state([s.tokens[-1] for s in rows], [len(s) - 1 for s in rows])
                 logits = self.m.forward_logits(len(rows)).clone()
                 self._p2p_guard()
-                for i, seq in enumerate(rows):
+                for seq in rows:
                     seq.num_computed_tokens = len(seq)
-                    self._finish_token(seq, logits[i])
+                self._finish_tokens(rows, logits)
         self.s.free_finished_sequence_groups()
         return out.kind
 
