@@ -2,6 +2,7 @@
 // ext_dec_gemv.hip (one translation unit per count: the instantiations are large), launched from ext_dec.hip.
 #pragma once
 #include "dec_core2.cuh"
+#include "dec_epilogue.cuh"
 #include <algorithm>
 
 namespace mrs {
@@ -17,10 +18,7 @@ struct GemvArgs {
   const float *x; int ldx; const float *norm_w; float eps;
   float *out; int out_stride; float resid_scale;
   int activation;
-  float *q_out; void *k_cache, *v_cache; const int64_t *slot_mapping; const int32_t *positions; const float *cos_t, *sin_t;
-  int head_dim, rot_pairs, num_kv_heads, block_size, cache_x, kv_f16;
-  int hd_shift, bs_shift, x_shift;  // log2 of head_dim / block_size / cache_x (the launcher refuses other values): the epilogue's index arithmetic is shifts and masks --
-                                    // with run-time divisors it was ~10 integer divisions per column and row pair (~40 VALU each), 10 us of the batch-8 qkv launch
+  QkvEpi qkv;     // EPI_QKV: RoPE tables, q output, paged K / V cache (dec_epilogue.cuh)
   int neox;       // EPI_QKV: rows of q / k are stored in PAIR order (original rows i, i + head_dim / 2 of a head adjacent): rotate-half RoPE; results go back to i, i + head_dim / 2
   int wg0[4];     // EPI_QKV: first workgroup of q, k, v and the total (a workgroup streams ONE tensor: the three may have different formats)
   const int32_t *expert_sel;  // stacked experts [E * nrows][K]: rows of expert e start at e * nrows (nullptr = dense)
@@ -141,7 +139,7 @@ __device__ __forceinline__ void gemv_phase(const GemvArgs &a, char *smem, float 
 #pragma unroll
         for (int c = 0; c < NCOLS; ++c) {
           float *o = a.out + (size_t)c * a.out_stride + row0 + rr;
-          if constexpr (EPI == EPI_RESID) *o = ax.a[c] * a.resid_scale + sum[c] * ascale;
+          if constexpr (EPI == EPI_RESID) *o = resid_fold(ax.a[c], a.resid_scale, sum[c], ascale);
           else {
             *o = sum[c];
             if constexpr (NCOLS == 1) { if (a.amax) { const unsigned long long key = pack_max_key(sum[c], row0 + rr); *best = key > *best ? key : *best; } }
@@ -167,8 +165,7 @@ __device__ __forceinline__ void gemv_phase(const GemvArgs &a, char *smem, float 
       if (seg == 0) {
         s0save = sum[0];
       } else if (own && rr < nvalid) {
-        const float h1 = ax.a[0] * a.resid_scale + s0save * w0;
-        a.out[row0 + rr] = h1 * 1.0f + sum[0] * w1;
+        a.out[row0 + rr] = resid_fold(resid_fold(ax.a[0], a.resid_scale, s0save, w0), 1.0f, sum[0], w1);
       }
     };
     MRS_DEC_TYPE_SWITCH(jb.mat[0].type, { stream<TT, 1, true, RING2>(jb, K, NCI, mode, smem, ctr, sbar, stage, auxf, epi); })
@@ -186,7 +183,7 @@ __device__ __forceinline__ void gemv_phase(const GemvArgs &a, char *smem, float 
         const int slot = a.slots > 1 ? row / a.nrows[0] : 0;
 #pragma unroll
         for (int c = 0; c < NCOLS; ++c)
-          a.out[(size_t)slot * a.slot_out_stride + (size_t)c * a.out_stride + (row - slot * a.nrows[0])] = (a.activation == 0 ? silu_engine(gsave[c]) : glu_act(gsave[c], a.activation)) * sum[c];
+          a.out[(size_t)slot * a.slot_out_stride + (size_t)c * a.out_stride + (row - slot * a.nrows[0])] = glu_value(gsave[c], sum[c], a.activation);
       }
     };
     MRS_DEC_TYPE_SWITCH(jb.mat[0].type, { stream<TT, NCOLS, false, RING2>(jb, K, NCI, mode, smem, ctr, sbar, stage, auxf, epi); })
@@ -194,18 +191,11 @@ __device__ __forceinline__ void gemv_phase(const GemvArgs &a, char *smem, float 
     // positions and KV slots: a handful of scalars, loaded before anything else; the RoPE factors travel with the record (owner lanes of the pair's two rows)
     int posv[NCOLS], slotv[NCOLS];  // slots are block * block_size + offset of a cache that fits 32-bit indexing per layer (checked by the launcher)
 #pragma unroll
-    for (int c = 0; c < NCOLS; ++c) { posv[c] = a.positions[c]; slotv[c] = mi == 0 ? 0 : (int)a.slot_mapping[c]; }
-    auto load_aux = [&](int row) {  // RoPE factors of the row's pair for every column; identity for v and unrotated dims (x*1 - y*0 = x exactly).  Unconditional loads.
+    for (int c = 0; c < NCOLS; ++c) { posv[c] = a.qkv.positions[c]; slotv[c] = mi == 0 ? 0 : (int)a.qkv.slot_mapping[c]; }
+    auto load_aux = [&](int row) {  // RoPE factors of the row's pair for every column
       AuxV<NCOLS> v;
-      const int pair_i = (row & (a.head_dim - 1)) >> 1;
-      const bool rot = mi < 2 && pair_i < a.rot_pairs;
-      const int pi = min(pair_i, a.rot_pairs - 1);
 #pragma unroll
-      for (int c = 0; c < NCOLS; ++c) {
-        const size_t ti = (size_t)posv[c] * a.rot_pairs + pi;
-        const float cs = a.cos_t[ti], sn = a.sin_t[ti];
-        v.a[c] = rot ? cs : 1.0f; v.b[c] = rot ? sn : 0.0f;
-      }
+      for (int c = 0; c < NCOLS; ++c) { const RopeCS f = qkv_rope_factors(a.qkv, mi, posv[c], row); v.a[c] = f.c; v.b[c] = f.s; }
       return v;
     };
     auto auxf = [&](int row0) {
@@ -226,10 +216,7 @@ __device__ __forceinline__ void gemv_phase(const GemvArgs &a, char *smem, float 
       const int row = row0 + rr;                   // this lane's row; its pair partner sits lpr lanes away (R = 1: in prev)
       const bool odd = single ? true : (row & 1) != 0;
       const int lr = single ? row - 1 : (row & ~1);  // even row of the pair
-      const int head = lr >> a.hd_shift, dd = lr & (a.head_dim - 1);
-      // where the two results live: adjacent dims (interleaved RoPE), or dims i and i + head_dim / 2 when the rows were stored in pair order (v: never)
-      const bool nx = a.neox && mi < 2;
-      const int d0 = nx ? dd >> 1 : dd, d1 = nx ? d0 + (a.head_dim >> 1) : dd + 1;
+      const QkvDst dst = qkv_dst(a.qkv, mi, a.neox, lr);
 #pragma unroll
       for (int c = 0; c < NCOLS; ++c) {
         const float other = single ? prev[c] : __shfl(sum[c], lane ^ lpr, 64);
@@ -237,29 +224,7 @@ __device__ __forceinline__ void gemv_phase(const GemvArgs &a, char *smem, float 
         float x, y;
         rope_pair<float>(xs, ys, ax.a[c], ax.b[c], x, y);
         const bool wr0 = single ? own : (own && rr < nvalid && !odd), wr1 = single ? own : (own && rr < nvalid && odd);  // R = 1: one lane writes both
-        if (wr0 || wr1) {
-          if (mi == 0) {
-            if (wr0) a.q_out[(size_t)c * a.nrows[0] + head * a.head_dim + d0] = x;
-            if (wr1) a.q_out[(size_t)c * a.nrows[0] + head * a.head_dim + d1] = y;
-          } else {
-            const int slot = slotv[c];
-            if (slot >= 0) {
-              const unsigned blk = (unsigned)slot >> a.bs_shift, off = (unsigned)slot & (unsigned)(a.block_size - 1);
-              uint16_t *kc = (uint16_t *)a.k_cache, *vc = (uint16_t *)a.v_cache;
-              const uint16_t xb = a.kv_f16 ? float_to_half_bits(x) : float_to_bf16_bits(x), yb = a.kv_f16 ? float_to_half_bits(y) : float_to_bf16_bits(y);
-              if (mi == 1) {
-                const int X = a.cache_x;
-                const size_t hb = ((size_t)blk * a.num_kv_heads + head) * (size_t)(a.head_dim >> a.x_shift);
-                if (wr0) kc[(hb + ((unsigned)d0 >> a.x_shift)) * a.block_size * X + off * X + ((unsigned)d0 & (unsigned)(X - 1))] = xb;
-                if (wr1) kc[(hb + ((unsigned)d1 >> a.x_shift)) * a.block_size * X + off * X + ((unsigned)d1 & (unsigned)(X - 1))] = yb;
-              } else {
-                const size_t o = (((size_t)blk * a.num_kv_heads + head) * a.head_dim + dd) * a.block_size + off;
-                if (wr0) vc[o] = xb;
-                if (wr1) vc[o + a.block_size] = yb;
-              }
-            }
-          }
-        }
+        if (wr0 || wr1) qkv_store(a.qkv, mi, a.nrows[0], c, slotv[c], dst, x, y, wr0, wr1);
       }
     };
     MRS_DEC_TYPE_SWITCH(jb.mat[0].type, { stream<TT, NCOLS, false, RING2>(jb, K, NCI, mode, smem, ctr, sbar, stage, auxf, epi); })
@@ -291,6 +256,14 @@ __global__ void __launch_bounds__(NT) dec_gemv_kernel(const GemvArgs a) {
   } else gemv_phase<NCOLS, EPI, TMASK, RING2>(a, smem, red, &ctr, nullptr);
 }
 
+
+// The column groups of a batch of b activation columns of K values: halved until a group's image fits the GEMV kernels' LDS.  mrs_dec_act_image writes one image per
+// group and every consumer (the GEMV launcher's column split, the matrix-core kernel's per-column offsets) finds a column through this one function.
+constexpr size_t LDS_IMG_MAX = (size_t)LDS_DYN_MAX;
+inline void col_groups(int K, int c0, int b, int *gc0, int *gn) {
+  if (b > 1 && act_bytes(K, b) > LDS_IMG_MAX) { col_groups(K, c0, b / 2, gc0, gn); col_groups(K, c0 + b / 2, b - b / 2, gc0, gn); return; }
+  for (int c = c0; c < c0 + b; ++c) { gc0[c] = c0; gn[c] = b; }
+}
 
 // launch one GEMV phase with NCOLS activation columns (ext_dec_gemv.hip, one definition per NCOLS)
 template <int NCOLS> int gemv_launch(int epi, int tmask, bool ring2, int grid, size_t lds, const GemvArgs &a, hipStream_t s);

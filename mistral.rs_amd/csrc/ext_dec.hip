@@ -253,12 +253,6 @@ __global__ void __launch_bounds__(NT) dec_act_image_kernel(const ActImgArgs a) {
   const int c0 = a.gc0[c], n = a.gn[c];
   act_quantize_all<1, 1>(a.img + act_bytes(a.K, c0), red, pre, x, a.ldx, a.norm_w, a.eps, a.K, a.mode, wave, c - c0, n);
 }
-// the column groups of a batch of b columns of K values: halved until a group's image fits LDS (the same recursion as Launch::run)
-constexpr size_t LDS_IMG_MAX = (size_t)158 * 1024;
-static void col_groups(int K, int c0, int b, int *gc0, int *gn) {
-  if (b > 1 && act_bytes(K, b) > LDS_IMG_MAX) { col_groups(K, c0, b / 2, gc0, gn); col_groups(K, c0 + b / 2, b - b / 2, gc0, gn); return; }
-  for (int c = c0; c < c0 + b; ++c) { gc0[c] = c0; gn[c] = b; }
-}
 
 // ------------------------------------------------------------------------------------------------ launch
 static unsigned long long *g_tl_buf = nullptr;
@@ -314,9 +308,9 @@ template <int EPI> struct Launch {
   static GemvArgs shift_cols(GemvArgs a, int c0) {
     if (a.x) a.x += (size_t)c0 * a.ldx;
     if (a.out) a.out += (size_t)c0 * a.out_stride;
-    if (a.q_out) a.q_out += (size_t)c0 * a.nrows[0];
-    if (a.positions) a.positions += c0;
-    if (a.slot_mapping) a.slot_mapping += c0;
+    if (a.qkv.q_out) a.qkv.q_out += (size_t)c0 * a.nrows[0];
+    if (a.qkv.positions) a.qkv.positions += c0;
+    if (a.qkv.slot_mapping) a.qkv.slot_mapping += c0;
     if (a.x_img) a.x_img = (const char *)a.x_img + act_bytes(a.K, c0);  // (mrs_dec_act_image writes one image per column group: col_groups)
     return a;
   }
@@ -376,16 +370,12 @@ static int dec_qkv_impl(const mrs_dec_mat_c *wq, const mrs_dec_mat_c *wk, const 
   if (neox && rot_pairs * 2 != head_dim) return -1;  // pair order (i, i + head_dim / 2) is the rotate-half pairing only when every dim rotates
   if (!wq || !wk || !wv || !make_mat(a.m[0], wq->planes, wq->type, wq->n, wq->k) || !make_mat(a.m[1], wk->planes, wk->type, wk->n, wk->k) ||
       !make_mat(a.m[2], wv->planes, wv->type, wv->n, wv->k)) return -1;
-  if (wq->k != wk->k || wq->k != wv->k || ((wq->n | wk->n | wv->n | head_dim) & 1)) return -1;
+  if (wq->k != wk->k || wq->k != wv->k) return -1;
   if (act_mode_for(wq->type) != act_mode_for(wk->type) || act_mode_for(wq->type) != act_mode_for(wv->type)) return -1;
-  if (kv_dtype != 0 && kv_dtype != 1) return -1;
+  if (!qkv_epi_fill(a.qkv, q_out, k_cache, v_cache, slot_mapping, positions, cos_t, sin_t, head_dim, rot_pairs, num_kv_heads, block_size, kv_dtype, wq->n, wk->n, wv->n))
+    return -1;
   a.nrows[0] = (int)wq->n; a.nrows[1] = (int)wk->n; a.nrows[2] = (int)wv->n; a.K = (int)wq->k;
-  a.x = h; a.ldx = ldh; a.norm_w = norm_w; a.eps = eps; a.q_out = q_out; a.k_cache = k_cache; a.v_cache = v_cache; a.slot_mapping = slot_mapping;
-  a.positions = positions; a.cos_t = cos_t; a.sin_t = sin_t; a.head_dim = head_dim; a.rot_pairs = rot_pairs; a.num_kv_heads = num_kv_heads;
-  a.block_size = block_size; a.cache_x = 8; a.kv_f16 = kv_dtype == 0;
-  auto lg2 = [](int v) { int s = 0; while ((1 << s) < v) ++s; return (1 << s) == v ? s : -1; };
-  a.hd_shift = lg2(head_dim); a.bs_shift = lg2(block_size); a.x_shift = lg2(a.cache_x);
-  if (a.hd_shift < 0 || a.bs_shift < 0 || head_dim < a.cache_x) return -1;  // powers of two (every head size the engine's attention takes, every block size of the reference's cache)
+  a.x = h; a.ldx = ldh; a.norm_w = norm_w; a.eps = eps;
   return Launch<EPI_QKV>::run(a, b, (hipStream_t)stream);
 }
 extern "C" int mrs_dec_qkv(const mrs_dec_mat_c *wq, const mrs_dec_mat_c *wk, const mrs_dec_mat_c *wv, const float *h, int ldh, const float *norm_w, float eps,

@@ -8,7 +8,7 @@ namespace mrs {
 namespace dec {
 template <int EPI, int NC, int TMASK = TM_ALL, bool RING2 = false> static void go1(int grid, size_t lds, const GemvArgs &a, hipStream_t s) {
   auto kern = dec_gemv_kernel<NC, EPI, TMASK, RING2>;
-  lds_attr_once((const void *)kern, 158 * 1024);
+  lds_attr_once((const void *)kern, LDS_DYN_MAX);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds, s, a);
 }
 // one or two format bodies per instantiation where the launch is latency-bound (batch 1); every format in one kernel for the batched launches

@@ -24,6 +24,7 @@ namespace mrs {
 namespace mm {
 using namespace mrs::dec2;
 using mrs::dec::EPI_STORE; using mrs::dec::EPI_RESID; using mrs::dec::EPI_GLU; using mrs::dec::EPI_QKV;
+using mrs::dec::QkvEpi; using mrs::dec::RopeCS; using mrs::dec::resid_fold; using mrs::dec::glu_value; using mrs::dec::qkv_rope_factors; using mrs::dec::qkv_dst; using mrs::dec::qkv_store;
 using mrs::dec::TM_Q4K; using mrs::dec::TM_Q5K; using mrs::dec::TM_Q6K; using mrs::dec::TM_Q80; using mrs::dec::tmask_of;
 
 typedef int i4v __attribute__((ext_vector_type(4)));
@@ -44,8 +45,7 @@ struct MmArgs {
   const char *img; unsigned gc0p, gnp;  // the image(s) mrs_dec_act_image wrote: column c lives in the group image at act_bytes(K, gc0), gn columns wide (gc0 / gn - 1: 4 bits per column; an
                                        // array indexed by a run-time column would make hipcc copy the whole argument block to scratch memory)
   float *out; int out_stride; float resid_scale; int activation;
-  float *q_out; void *k_cache, *v_cache; const int64_t *slot_mapping; const int32_t *positions; const float *cos_t, *sin_t;
-  int head_dim, rot_pairs, num_kv_heads, block_size, cache_x, kv_f16, hd_shift, bs_shift, x_shift;
+  QkvEpi qkv;    // EPI_QKV (dec_epilogue.cuh)
   unsigned long long *tl;  // experiments: 8 s_memrealtime stamps (100 MHz) per wave, or nullptr (mrs_dec_mm_timeline)
 };
 #ifdef MRS_MM_TIMELINE  // (a conditional store inside the streaming loop makes every wait of the ring stricter: off in the product build)
@@ -260,46 +260,20 @@ __device__ __forceinline__ void finish_unit(const MmArgs &a, const float *ex, in
   const int nrows = ti == 0 ? nr0 : (ti == 1 ? nr1 : nr2);
   const bool ok = tok < nc && n < nrows;
   if (epi == EPI_STORE) { if (ok) a.out[(size_t)tok * a.out_stride + n] = sum; }
-  else if (epi == EPI_RESID) { if (ok) { float *o = a.out + (size_t)tok * a.out_stride + n; *o = *o * a.resid_scale + sum * 1.0f; } }
+  else if (epi == EPI_RESID) { if (ok) { float *o = a.out + (size_t)tok * a.out_stride + n; *o = resid_fold(*o, a.resid_scale, sum, 1.0f); } }
   else if (epi == EPI_GLU) {
     if (eseg == 0) gsave = sum;
-    else if (ok) a.out[(size_t)tok * a.out_stride + n] = (a.activation == 0 ? silu_engine(gsave) : glu_act(gsave, a.activation)) * sum;
-  } else {  // EPI_QKV, interleaved RoPE: rows 2 i, 2 i + 1 are a pair = lanes l, l ^ 1 of this wave (dec_gemv.cuh EPI_QKV, R >= 2)
+    else if (ok) a.out[(size_t)tok * a.out_stride + n] = glu_value(gsave, sum, a.activation);
+  } else {  // EPI_QKV, interleaved RoPE: rows 2 i, 2 i + 1 are a pair = lanes l, l ^ 1 of this wave (dec_gemv.cuh EPI_QKV, R >= 2); every live lane writes its own row
     const float other = __shfl_xor(sum, 1, 64);
     if (ok) {
-      const int c = tok;
       const bool odd = (n & 1) != 0;
-      const int lr = n & ~1, head = lr >> a.hd_shift, dd = lr & (a.head_dim - 1);
-      const int pair_i = dd >> 1;
-      const bool rot = ti < 2 && pair_i < a.rot_pairs;
-      const int pi = min(pair_i, a.rot_pairs - 1);
-      const size_t tix = (size_t)a.positions[c] * a.rot_pairs + pi;
-      const float cs = a.cos_t[tix], sn = a.sin_t[tix];
-      const float ca = rot ? cs : 1.0f, sa = rot ? sn : 0.0f;
+      const RopeCS f = qkv_rope_factors(a.qkv, ti, a.qkv.positions[tok], n);
       const float xs = odd ? other : sum, ys = odd ? sum : other;
       float x, y;
-      rope_pair<float>(xs, ys, ca, sa, x, y);
-      const int d0 = dd, d1 = dd + 1;
-      if (ti == 0) {
-        if (!odd) a.q_out[(size_t)c * nr0 + head * a.head_dim + d0] = x;
-        else a.q_out[(size_t)c * nr0 + head * a.head_dim + d1] = y;
-      } else {
-        const int slot = (int)a.slot_mapping[c];
-        if (slot >= 0) {
-          const unsigned blk = (unsigned)slot >> a.bs_shift, off = (unsigned)slot & (unsigned)(a.block_size - 1);
-          uint16_t *kc = (uint16_t *)a.k_cache, *vc = (uint16_t *)a.v_cache;
-          const uint16_t xb = a.kv_f16 ? float_to_half_bits(x) : float_to_bf16_bits(x), yb = a.kv_f16 ? float_to_half_bits(y) : float_to_bf16_bits(y);
-          if (ti == 1) {
-            const int X = a.cache_x;
-            const size_t hb = ((size_t)blk * a.num_kv_heads + head) * (size_t)(a.head_dim >> a.x_shift);
-            if (!odd) kc[(hb + ((unsigned)d0 >> a.x_shift)) * a.block_size * X + off * X + ((unsigned)d0 & (unsigned)(X - 1))] = xb;
-            else kc[(hb + ((unsigned)d1 >> a.x_shift)) * a.block_size * X + off * X + ((unsigned)d1 & (unsigned)(X - 1))] = yb;
-          } else {
-            const size_t o = (((size_t)blk * a.num_kv_heads + head) * a.head_dim + dd) * a.block_size + off;
-            if (!odd) vc[o] = xb; else vc[o + a.block_size] = yb;
-          }
-        }
-      }
+      rope_pair<float>(xs, ys, f.c, f.s, x, y);
+      const int slot = ti == 0 ? 0 : (int)a.qkv.slot_mapping[tok];
+      qkv_store(a.qkv, ti, nr0, tok, slot, qkv_dst(a.qkv, ti, 0, n & ~1), x, y, !odd, odd);
     }
   }
 }
@@ -510,14 +484,14 @@ static int launch(const MmArgs &a0, hipStream_t s) {
   for (int i = nt; i < 3; ++i) { a.m[i] = a.m[0]; a.m[i].bytes = 0; a.m[i].npanels = 0; }
   if (a.K <= 0 || a.K % 256 || a.nc < 1 || a.nc > 8 || !a.img || a.units < 1) return -1;
   const size_t lds = (lds_bytes(a.K, a.nc, a.mode) + 15) & ~(size_t)15;
-  if (lds > (size_t)158 * 1024) return -2;
+  if (lds > (size_t)LDS_DYN_MAX) return -2;
   constexpr int wg_per_cu = 2;
   const int fit = (tmask == TM_Q4K || tmask == TM_Q5K || tmask == TM_Q80) ? 2 : 1;  // workgroups per CU the kernel's registers admit (see the kernels above)
   const int cap = 256 * std::min<int>(std::min(wg_per_cu, fit), std::max<size_t>(1, ((size_t)160 * 1024) / lds));
   const int grid = std::min(a.units, cap);
   auto go = [&](auto kern) {
     ++g_mm_launches;
-    lds_attr_once((const void *)kern, 158 * 1024);
+    lds_attr_once((const void *)kern, LDS_DYN_MAX);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(MT), lds, s, a);
     return hipGetLastError() == hipSuccess ? 0 : -4;
   };
@@ -532,11 +506,6 @@ static int launch(const MmArgs &a0, hipStream_t s) {
   }
 }
 
-// the column groups mrs_dec_act_image wrote (ext_dec.hip col_groups: halved until a group's image fits the GEMV kernels' LDS)
-static void col_groups(int K, int c0, int b, int *gc0, int *gn) {
-  if (b > 1 && act_bytes(K, b) > (size_t)158 * 1024) { col_groups(K, c0, b / 2, gc0, gn); col_groups(K, c0 + b / 2, b - b / 2, gc0, gn); return; }
-  for (int c = c0; c < c0 + b; ++c) { gc0[c] = c0; gn[c] = b; }
-}
 static bool set_tensor(MmTensor &t, const void *qi, int type, long long n, long long k) {
   if (!qi || !mm_type(type) || n <= 0 || k <= 0 || k % 256) return false;
   const size_t bytes = (size_t)((n + 31) / 32) * (size_t)(k / 256) * rec_bytes(type);
@@ -548,7 +517,7 @@ static bool base(MmArgs &a, const void *x_img, int k, int b, int type0) {
   if (!x_img || b < 1 || b > 8 || ((uintptr_t)x_img & 15)) return false;
   a.K = k; a.nc = b; a.img = (const char *)x_img; a.mode = act_mode_for(type0);
   int gc0[8] = {0}, gn[8] = {1, 1, 1, 1, 1, 1, 1, 1};
-  col_groups(k, 0, b, gc0, gn);
+  mrs::dec::col_groups(k, 0, b, gc0, gn);  // where mrs_dec_act_image put each column
   for (int c = 0; c < b; ++c) { a.gc0p |= (unsigned)gc0[c] << (4 * c); a.gnp |= (unsigned)(gn[c] - 1) << (4 * c); }
   return true;
 }
@@ -564,7 +533,7 @@ extern "C" void mrs_dec_mm_timeline(void *buf) { g_mm_tl = (unsigned long long *
 // Can the batched matrix-core route take a launch of this weight type / reduction length / column count?  (K-quants and Q8_0; the LDS budget bounds k x b)
 extern "C" int mrs_dec_mm_supported(int type, int k, int b) {
   if (!mm_type(type) || k <= 0 || k % 256 || b < 1 || b > 8) return 0;
-  return lds_bytes(k, b, dec2::act_mode_for(type)) + 15 <= (size_t)158 * 1024 ? 1 : 0;
+  return lds_bytes(k, b, dec2::act_mode_for(type)) + 15 <= (size_t)LDS_DYN_MAX ? 1 : 0;
 }
 // out [b][ld_out] = W . x (mode 0) or out * resid_scale + W . x (mode 1); qi = the MFMA-order copy of W (mrs_gemm_qi_repack), x_img = mrs_dec_act_image(.., type, b, ..)
 extern "C" int mrs_dec_mm_proj(const void *qi, int type, int n, int k, const void *x_img, float *out, int ld_out, int mode, float resid_scale, int b, void *stream) {
@@ -588,12 +557,8 @@ extern "C" int mrs_dec_mm_qkv(const void *qi_q, int type_q, int nq, const void *
   MmArgs a{};
   if (!q_out || !k_cache || !v_cache || !slot_mapping || !positions || !cos_t || !sin_t) return -1;
   if (!set_tensor(a.m[0], qi_q, type_q, nq, k) || !set_tensor(a.m[1], qi_k, type_k, nk, k) || !set_tensor(a.m[2], qi_v, type_v, nv, k) || !base(a, x_img, k, b, type_q)) return -1;
-  if (((nq | nk | nv | head_dim) & 1) || (kv_dtype != 0 && kv_dtype != 1)) return -1;
-  auto lg2 = [](int v) { int s = 0; while ((1 << s) < v) ++s; return (1 << s) == v ? s : -1; };
+  if (!mrs::dec::qkv_epi_fill(a.qkv, q_out, k_cache, v_cache, slot_mapping, positions, cos_t, sin_t, head_dim, rot_pairs, num_kv_heads, block_size, kv_dtype, nq, nk, nv))
+    return -1;
   a.epi = EPI_QKV; a.nseg = 1; a.units = a.m[0].npanels + a.m[1].npanels + a.m[2].npanels;
-  a.q_out = q_out; a.k_cache = k_cache; a.v_cache = v_cache; a.slot_mapping = slot_mapping; a.positions = positions; a.cos_t = cos_t; a.sin_t = sin_t;
-  a.head_dim = head_dim; a.rot_pairs = rot_pairs; a.num_kv_heads = num_kv_heads; a.block_size = block_size; a.cache_x = 8; a.kv_f16 = kv_dtype == 0;
-  a.hd_shift = lg2(head_dim); a.bs_shift = lg2(block_size); a.x_shift = lg2(a.cache_x);
-  if (a.hd_shift < 0 || a.bs_shift < 0 || head_dim < a.cache_x || rot_pairs < 1) return -1;
   return launch(a, (hipStream_t)stream);
 }

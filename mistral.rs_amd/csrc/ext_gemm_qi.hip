@@ -24,6 +24,7 @@
 // tokens, wave 32 x 64 = 1 x 2 MFMA tiles; per superblock the 128 tokens' f16 quants (64 KiB) are staged in LDS (16-byte chunks XOR-swizzled by the token
 // index: conflict-free ds_read_b128 fragments), double buffered: superblock s + 1 arrives by LDS-DMA (global_load_lds) while s is multiplied.
 #include "dec_core2.cuh"
+#include "dec_epilogue.cuh"
 #include <stdio.h>
 #include <stdlib.h>
 #include <algorithm>
@@ -721,9 +722,9 @@ extern "C" int mrs_qi_quantize_for(int w_type, const float *x, const float *x2, 
   a.x = x; a.x2 = x2; a.ldx = ldx; a.norm_w = norm_w; a.eps = eps; a.K = K; a.T = T; a.xtmp = xtmp; a.mode = dec2::act_mode_for(w_type);
   qi_split(act, T, K, &a.qf, &a.yd, &a.bsf);
   const size_t lds = (dec2::act_bytes(K, 1) + 15) & ~(size_t)15;
-  if (lds > 158 * 1024) return -2;
-  if (x2) { auto kern = qi::qi_quantize_kernel<true>; lds_attr_once((const void *)kern, 158 * 1024); hipLaunchKernelGGL(kern, dim3(T), dim3(dec2::NT), lds, (hipStream_t)stream, a); }
-  else { auto kern = qi::qi_quantize_kernel<false>; lds_attr_once((const void *)kern, 158 * 1024); hipLaunchKernelGGL(kern, dim3(T), dim3(dec2::NT), lds, (hipStream_t)stream, a); }
+  if (lds > LDS_DYN_MAX) return -2;
+  if (x2) { auto kern = qi::qi_quantize_kernel<true>; lds_attr_once((const void *)kern, LDS_DYN_MAX); hipLaunchKernelGGL(kern, dim3(T), dim3(dec2::NT), lds, (hipStream_t)stream, a); }
+  else { auto kern = qi::qi_quantize_kernel<false>; lds_attr_once((const void *)kern, LDS_DYN_MAX); hipLaunchKernelGGL(kern, dim3(T), dim3(dec2::NT), lds, (hipStream_t)stream, a); }
   return 0;
 }
 // out[t * ldo + n] (+)= W[n] . act[t] for t < T, n < N in the decode engine's arithmetic and f32 order.  w_qi: mrs_gemm_qi_repack output; act: mrs_qi_quantize output.
@@ -760,10 +761,10 @@ static int gemm_qi_launch(const void *w_qi, int type, int N, int K, const void *
   constexpr int split_max = 200;
   a.ksplit = 1; a.part = nullptr;
   if (!win && (int)(grid.x * grid.y) < split_max && K / 256 >= 4 && N % 4 == 0 && workspace && workspace_bytes >= (size_t)4 * T * N * 4) { a.ksplit = 4; a.part = (float *)workspace; grid.z = 4; }
-  if (type == T_Q8_0) { auto kern = qi::gemm_q80_kernel; lds_attr_once((const void *)kern, 158 * 1024); hipLaunchKernelGGL(kern, grid, dim3(qi::GT), qi::L8_TOTAL, (hipStream_t)stream, a); }
-  else if (type == T_Q4_K) { auto kern = qi::gemm_qi_kernel<T_Q4_K>; lds_attr_once((const void *)kern, 158 * 1024); hipLaunchKernelGGL(kern, grid, dim3(qi::GT), qi::LDS_TOTAL, (hipStream_t)stream, a); }
-  else if (type == T_Q5_K) { auto kern = qi::gemm_qi_kernel<T_Q5_K>; lds_attr_once((const void *)kern, 158 * 1024); hipLaunchKernelGGL(kern, grid, dim3(qi::GT), qi::LDS_TOTAL, (hipStream_t)stream, a); }
-  else { auto kern = qi::gemm_qi_kernel<T_Q6_K>; lds_attr_once((const void *)kern, 158 * 1024); hipLaunchKernelGGL(kern, grid, dim3(qi::GT), qi::LDS_TOTAL, (hipStream_t)stream, a); }
+  if (type == T_Q8_0) { auto kern = qi::gemm_q80_kernel; lds_attr_once((const void *)kern, LDS_DYN_MAX); hipLaunchKernelGGL(kern, grid, dim3(qi::GT), qi::L8_TOTAL, (hipStream_t)stream, a); }
+  else if (type == T_Q4_K) { auto kern = qi::gemm_qi_kernel<T_Q4_K>; lds_attr_once((const void *)kern, LDS_DYN_MAX); hipLaunchKernelGGL(kern, grid, dim3(qi::GT), qi::LDS_TOTAL, (hipStream_t)stream, a); }
+  else if (type == T_Q5_K) { auto kern = qi::gemm_qi_kernel<T_Q5_K>; lds_attr_once((const void *)kern, LDS_DYN_MAX); hipLaunchKernelGGL(kern, grid, dim3(qi::GT), qi::LDS_TOTAL, (hipStream_t)stream, a); }
+  else { auto kern = qi::gemm_qi_kernel<T_Q6_K>; lds_attr_once((const void *)kern, LDS_DYN_MAX); hipLaunchKernelGGL(kern, grid, dim3(qi::GT), qi::LDS_TOTAL, (hipStream_t)stream, a); }
   if (a.ksplit > 1) hipLaunchKernelGGL(qi::gemm_qi_reduce_kernel, dim3((unsigned)(((size_t)T * N / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a.part, out, T, N, ldo, accumulate);
   return 0;
 }
@@ -808,7 +809,7 @@ __global__ void __launch_bounds__(256) moe_fold_exact_kernel(float *__restrict__
     for (int sl = 0; sl < tk; ++sl) {
       const float ws = w[(size_t)t * tk + sl], sc = sl == 0 ? rs : 1.0f;
       const float4 yy = *(const float4 *)(y + (size_t)inv[(size_t)t * tk + sl] * d + n);
-      v.x = v.x * sc + yy.x * ws; v.y = v.y * sc + yy.y * ws; v.z = v.z * sc + yy.z * ws; v.w = v.w * sc + yy.w * ws;
+      v.x = dec::resid_fold(v.x, sc, yy.x, ws); v.y = dec::resid_fold(v.y, sc, yy.y, ws); v.z = dec::resid_fold(v.z, sc, yy.z, ws); v.w = dec::resid_fold(v.w, sc, yy.w, ws);
     }
     *(float4 *)(h + (size_t)t * d + n) = v;
   }
@@ -818,9 +819,9 @@ __global__ void __launch_bounds__(256) resid_scale_add_kernel(float *__restrict_
   for (size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4; i < n; i += (size_t)gridDim.x * 1024) {
     if (i + 4 <= n) {
       float4 a = *(float4 *)(h + i); const float4 b = *(const float4 *)(y + i);
-      a.x = a.x * rs + b.x * 1.0f; a.y = a.y * rs + b.y * 1.0f; a.z = a.z * rs + b.z * 1.0f; a.w = a.w * rs + b.w * 1.0f;
+      a.x = dec::resid_fold(a.x, rs, b.x, 1.0f); a.y = dec::resid_fold(a.y, rs, b.y, 1.0f); a.z = dec::resid_fold(a.z, rs, b.z, 1.0f); a.w = dec::resid_fold(a.w, rs, b.w, 1.0f);
       *(float4 *)(h + i) = a;
-    } else for (size_t j = i; j < n; ++j) h[j] = h[j] * rs + y[j] * 1.0f;
+    } else for (size_t j = i; j < n; ++j) h[j] = dec::resid_fold(h[j], rs, y[j], 1.0f);
   }
 }
 }  // namespace qi
@@ -1181,10 +1182,10 @@ extern "C" int mrs_prefill_attention_exact(const float *q, const void *k_cache, 
   {
     const int nb = (need_ctx + 31) / 32;
     const size_t lds_m = (size_t)mrs::qi::PM_Q + mrs::qi::PM_P + mrs::qi::PM_SC + (size_t)nb * 128;
-    if (lds_m <= 158 * 1024) {
+    if (lds_m <= mrs::LDS_DYN_MAX) {
       const dim3 gm(num_heads, (T + 31) / 32);
-      if (kv_dtype == 1) { auto kern = mrs::qi::prefill_attn_mfma_kernel<mrs::bf16_t>; mrs::lds_attr_once((const void *)kern, 158 * 1024); hipLaunchKernelGGL(kern, gm, dim3(64 * mrs::qi::PM_NW), lds_m, (hipStream_t)stream, a, nb); }
-      else { auto kern = mrs::qi::prefill_attn_mfma_kernel<mrs::f16_t>; mrs::lds_attr_once((const void *)kern, 158 * 1024); hipLaunchKernelGGL(kern, gm, dim3(64 * mrs::qi::PM_NW), lds_m, (hipStream_t)stream, a, nb); }
+      if (kv_dtype == 1) { auto kern = mrs::qi::prefill_attn_mfma_kernel<mrs::bf16_t>; mrs::lds_attr_once((const void *)kern, mrs::LDS_DYN_MAX); hipLaunchKernelGGL(kern, gm, dim3(64 * mrs::qi::PM_NW), lds_m, (hipStream_t)stream, a, nb); }
+      else { auto kern = mrs::qi::prefill_attn_mfma_kernel<mrs::f16_t>; mrs::lds_attr_once((const void *)kern, mrs::LDS_DYN_MAX); hipLaunchKernelGGL(kern, gm, dim3(64 * mrs::qi::PM_NW), lds_m, (hipStream_t)stream, a, nb); }
       return 0;
     }
   }
@@ -1192,11 +1193,11 @@ extern "C" int mrs_prefill_attention_exact(const float *q, const void *k_cache, 
   auto lds_for = [&](int w) { return 4 * ((size_t)w * G * 128 * 2 + (size_t)G * 32 + (size_t)w * G * a.max_splits * 2 + (size_t)w * G * 64) * 4; };
   while (qw > 1 && (lds_for(qw) > 76 * 1024 || (T + 4 * qw - 1) / (4 * qw) * num_kv_heads < 512)) --qw;  // two workgroups per CU, and enough workgroups to fill the chip
   const size_t lds = lds_for(qw);
-  if (lds > 158 * 1024) return -2;
+  if (lds > mrs::LDS_DYN_MAX) return -2;
   const dim3 grid(num_kv_heads, (T + 4 * qw - 1) / (4 * qw));
   hipStream_t s = (hipStream_t)stream;
-#define MRS_PA(GG, CT) { if (a.bpw == 1) { auto kern = mrs::qi::prefill_attn_exact_kernel<GG, CT, true>; mrs::lds_attr_once((const void *)kern, 158 * 1024); hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, a, qw); } \
-                         else { auto kern = mrs::qi::prefill_attn_exact_kernel<GG, CT, false>; mrs::lds_attr_once((const void *)kern, 158 * 1024); hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, a, qw); } }
+#define MRS_PA(GG, CT) { if (a.bpw == 1) { auto kern = mrs::qi::prefill_attn_exact_kernel<GG, CT, true>; mrs::lds_attr_once((const void *)kern, mrs::LDS_DYN_MAX); hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, a, qw); } \
+                         else { auto kern = mrs::qi::prefill_attn_exact_kernel<GG, CT, false>; mrs::lds_attr_once((const void *)kern, mrs::LDS_DYN_MAX); hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, a, qw); } }
 #define MRS_PAG(CT) switch (G) { case 1: MRS_PA(1, CT) break; case 2: MRS_PA(2, CT) break; case 4: MRS_PA(4, CT) break; default: MRS_PA(8, CT) break; }
   if (kv_dtype == 1) { MRS_PAG(mrs::bf16_t) } else { MRS_PAG(mrs::f16_t) }
 #undef MRS_PAG

@@ -136,8 +136,8 @@ template <int BITS, class T> static int launch(const Args &a, int b, hipStream_t
   const dim3 grid(a.N / 64, a.rsplit), block(NT);
   auto go = [&](auto kern, int ncols) {
     const size_t lds = (size_t)ncols * a.K * 4 + 2 * CH * 4;
-    if (lds > 158 * 1024) return -2;
-    lds_attr_once((const void *)kern, 158 * 1024);
+    if (lds > LDS_DYN_MAX) return -2;
+    lds_attr_once((const void *)kern, LDS_DYN_MAX);
     hipLaunchKernelGGL(kern, grid, block, lds, s, a);
     return 0;
   };

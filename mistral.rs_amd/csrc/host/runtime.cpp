@@ -428,6 +428,75 @@ class Llama {
     }
     return true;
   }
+  // ---- which kernel runs a linear of a decode step.  This is the one place that decides it; that the choice never shows in a token's bits is csrc/dec_epilogue.cuh.
+  struct Lin {               // a linear as the three kernels see it
+    const mrs_dec_mat *mat;  // decode-layout planes (vector-ALU GEMV)
+    const void *qi;          // MFMA-order copy the exact prompt path keeps (QTensor::qi), or nullptr
+    int k;                   // reduction length
+  };
+  static Lin lin(const mrs_dec_mat &m, const std::unique_ptr<GgufMatMul> &l, int k) { return Lin{&m, l && l->get_qtensor() ? l->get_qtensor()->qi : nullptr, k}; }
+  enum Route {  // ordered: a launch over several tensors takes the least of their routes
+    R_INLINE,     // the GEMV normalises + quantizes its activations itself (batch 1)
+    R_IMG_VALU,   // activation image built once (mrs_dec_act_image) + the vector-ALU GEMV
+    R_IMG_MM      // the same image + the matrix-core kernel (ext_dec_mm.hip)
+  };
+  static Route route(const Lin &l, int b) {
+    // Batched steps: every GEMV workgroup would normalise + quantize all b activation columns itself (256 times the same work, 17-25 us of a 40-60 us launch at
+    // b = 8); from 2 columns on the image of a phase is built once by mrs_dec_act_image (b workgroups) and the GEMVs copy it -- same bytes.
+    if (b < 2 || b > 8) return R_INLINE;
+    // (round 6) batched steps on the matrix cores: the same launches on the MFMA-order copy of the weights -- integer dots on v_mfma_i32_32x32x32_i8 instead of 535 VALU
+    // per 8-column tile, the same bits.  Batch 2 stays on the vector-ALU kernels.
+    constexpr int mm_min_b = 3;  // measured (MI355X, 8B Q4_K_M): batch 2 / 3 / 4 / 8 = 760 / 1128 / 1518 / 2722 tok/s here, 824 / 1103 / 1315 / 1685 on the vector ALU
+    return b >= mm_min_b && l.qi && mrs_dec_mm_supported(l.mat->type, l.k, b) ? R_IMG_MM : R_IMG_VALU;
+  }
+  // The phases of a step.  Each builds the activation image when its route needs one, then makes ONE launch; the three kernels of a phase share a contract.
+  int act_image(const float *x, const float *norm_w, const Lin &l, int b, hipStream_t s) const {
+    return mrs_dec_act_image(x, l.k, norm_w, cfg.rms_eps, l.k, l.mat->type, b, ws.act_img, s);
+  }
+  // RmsNorm(h) -> q (f32, RoPE applied) + k / v into the layer's pages.  The matrix cores only when all three tensors qualify and RoPE is interleaved (a rotate-half pair
+  // spans two panels); rotate-half: the caller registered q / k decode planes in pair order (mrs_dec_qkv_neox; llama.py permutes the rows before the repack)
+  int qkv_phase(const Block &bl, int b, hipStream_t s) const {
+    const int d = cfg.hidden_size, hd = cfg.head_dim, rp = cfg.rot_dim / 2, kvh = cfg.num_kv_heads, bs = cfg.block_size, kvd = cfg.kv_f16 ? 0 : 1;
+    const Lin q = lin(bl.dq, bl.q_proj, d), k = lin(bl.dk, bl.k_proj, d), v = lin(bl.dv, bl.v_proj, d);
+    Route r = std::min(route(q, b), std::min(route(k, b), route(v, b)));
+    if (r == R_IMG_MM && !cfg.rope_interleaved) r = R_IMG_VALU;
+    if (r != R_INLINE && act_image(ws.h, bl.input_layernorm, q, b, s)) return -1;
+    switch (r) {
+    case R_INLINE: return (cfg.rope_interleaved ? mrs_dec_qkv : mrs_dec_qkv_neox)(q.mat, k.mat, v.mat, ws.h, d, bl.input_layernorm, cfg.rms_eps, ws.q, bl.key_cache, bl.value_cache,
+                                                                              bufs.slot_mapping, bufs.positions, bufs.cos_table, bufs.sin_table, hd, rp, kvh, bs, kvd, b, s);
+    case R_IMG_VALU: return mrs_dec_qkv_img(q.mat, k.mat, v.mat, ws.act_img, ws.q, bl.key_cache, bl.value_cache, bufs.slot_mapping, bufs.positions, bufs.cos_table, bufs.sin_table,
+                                          hd, rp, kvh, bs, kvd, b, cfg.rope_interleaved ? 0 : 1, s);
+    default: return mrs_dec_mm_qkv(q.qi, q.mat->type, (int)q.mat->n, k.qi, k.mat->type, (int)k.mat->n, v.qi, v.mat->type, (int)v.mat->n, d, ws.act_img, ws.q, bl.key_cache,
+                                   bl.value_cache, bufs.slot_mapping, bufs.positions, bufs.cos_table, bufs.sin_table, hd, rp, kvh, bs, kvd, b, s);
+    }
+  }
+  // out [b][n] = W . x (mode 0) or out * rs + W . x (mode 1): o_proj, down, lm_head.  The source is x [b][k] f32 (-> RmsNorm when norm_w), or -- x == nullptr -- an image
+  // its producer already wrote (attention's attn_img), which the GEMV copies at every batch size.
+  int proj_phase(const Lin &l, int n, const float *x, const float *norm_w, const void *img, float *out, int mode, float rs, int b, hipStream_t s, Route r) const {
+    if (!x && r == R_INLINE) r = R_IMG_VALU;
+    if (x && r != R_INLINE) {
+      if (act_image(x, norm_w, l, b, s)) return -1;
+      img = ws.act_img;
+    }
+    switch (r) {
+    case R_INLINE: return mrs_dec_proj(l.mat, n, nullptr, x, l.k, norm_w, norm_w ? cfg.rms_eps : 0.f, out, n, mode, rs, nullptr, b, s);
+    case R_IMG_VALU: return mrs_dec_proj_img(l.mat, n, img, out, n, mode, rs, b, s);
+    default: return mrs_dec_mm_proj(l.qi, l.mat->type, n, l.k, img, out, n, mode, rs, b, s);
+    }
+  }
+  // RmsNorm(h) -> act = SiLU(W_g . x) * (W_u . x); the matrix cores only when both tensors qualify
+  int gate_up_phase(const Block &bl, int b, hipStream_t s) const {
+    const int d = cfg.hidden_size, ff = cfg.intermediate_size;
+    const Lin g = lin(bl.dgate, bl.gate_proj, d), u = lin(bl.dup, bl.up_proj, d);
+    const Route r = std::min(route(g, b), route(u, b));
+    if (r != R_INLINE && act_image(ws.h, bl.post_attention_layernorm, g, b, s)) return -1;
+    switch (r) {
+    case R_INLINE: return mrs_dec_gate_up(g.mat, u.mat, ff, nullptr, ws.h, d, bl.post_attention_layernorm, cfg.rms_eps, 0, ws.act, ff, b, s);
+    case R_IMG_VALU: return mrs_dec_gate_up_img(g.mat, u.mat, ff, ws.act_img, 0, ws.act, ff, b, s);
+    default: return mrs_dec_mm_gate_up(g.qi, u.qi, g.mat->type, ff, d, ws.act_img, 0, ws.act, ff, b, s);
+    }
+  }
+
   // chained (round 6, batch 1): ws.h already holds the embedding row of input_ids (the previous step's mrs_sample_advance_embed, or mrs_llama_embed_state after the host
   // changed the state) and lm_head folds the arg-max into its epilogue: the captured step is two launches shorter (no embedding_kernel, no argmax_partial_kernel)
   int forward_engine(int b, hipStream_t s, bool chained = false) const {
@@ -437,41 +506,18 @@ class Llama {
     const int eff_max = std::min(cfg.max_blocks_per_seq * bs, cfg.max_context_len);
     if (chained && b != 1) return fail("chained decode step: batch 1 only");
     if (!chained && wte->embedding_forward_raw(bufs.input_ids, b, ws.h, s)) return -1;
-    // Batched steps: every GEMV workgroup would normalise + quantize all b activation columns itself (256 times the same work, 17-25 us of a 40-60 us launch at
-    // b = 8); from 2 columns on the image of a phase is built once by mrs_dec_act_image (b workgroups) and the GEMVs copy it -- same bytes.
-    const bool imgb = b >= 2 && b <= 8;
-    auto image = [&](const float *x, int ldx, const float *nw, int k, int wtype) { return mrs_dec_act_image(x, ldx, nw, cfg.rms_eps, k, wtype, b, ws.act_img, s); };
-    // (round 6) batched steps on the matrix cores (ext_dec_mm.hip): the same launches on the MFMA-order copy of the weights the exact prompt path keeps (QTensor::qi) -- integer
-    // dots on v_mfma_i32_32x32x32_i8 instead of 535 VALU per 8-column tile, the same bits.  Batch 2 stays on the vector-ALU kernels.
-    constexpr int mm_min_b = 3;  // measured (MI355X, 8B Q4_K_M): batch 2 / 3 / 4 / 8 = 760 / 1128 / 1518 / 2722 tok/s here, 824 / 1103 / 1315 / 1685 on the vector ALU
-    const bool mmb = imgb && b >= mm_min_b;
-    auto qi_of = [](const std::unique_ptr<GgufMatMul> &l) -> const void * { return l && l->get_qtensor() ? l->get_qtensor()->qi : nullptr; };
-    auto mm_ok = [&](const void *qi, int type, int k) { return mmb && qi && mrs_dec_mm_supported(type, k, b); };
     for (const Block &bl : blocks) {
-      // rotate-half RoPE: the caller registered q / k decode planes in pair order (mrs_dec_qkv_neox; llama.py permutes the rows before the repack)
-      if (imgb && cfg.rope_interleaved && mm_ok(qi_of(bl.q_proj), bl.dq.type, d) && mm_ok(qi_of(bl.k_proj), bl.dk.type, d) && mm_ok(qi_of(bl.v_proj), bl.dv.type, d)) {
-        if (image(ws.h, d, bl.input_layernorm, d, bl.dq.type) ||
-            mrs_dec_mm_qkv(qi_of(bl.q_proj), bl.dq.type, (int)bl.dq.n, qi_of(bl.k_proj), bl.dk.type, (int)bl.dk.n, qi_of(bl.v_proj), bl.dv.type, (int)bl.dv.n, d, ws.act_img, ws.q,
-                           bl.key_cache, bl.value_cache, bufs.slot_mapping, bufs.positions, bufs.cos_table, bufs.sin_table, hd, cfg.rot_dim / 2, kvh, bs, kvd, b, s))
-          return fail("mrs_dec_mm_qkv refused the layer");
-      } else if (imgb) {
-        if (image(ws.h, d, bl.input_layernorm, d, bl.dq.type) ||
-            mrs_dec_qkv_img(&bl.dq, &bl.dk, &bl.dv, ws.act_img, ws.q, bl.key_cache, bl.value_cache, bufs.slot_mapping, bufs.positions, bufs.cos_table, bufs.sin_table, hd,
-                            cfg.rot_dim / 2, kvh, bs, kvd, b, cfg.rope_interleaved ? 0 : 1, s))
-          return fail("mrs_dec_qkv_img refused the layer");
-      } else if ((cfg.rope_interleaved ? mrs_dec_qkv : mrs_dec_qkv_neox)(&bl.dq, &bl.dk, &bl.dv, ws.h, d, bl.input_layernorm, cfg.rms_eps, ws.q, bl.key_cache, bl.value_cache,
-                                                                  bufs.slot_mapping, bufs.positions, bufs.cos_table, bufs.sin_table, hd, cfg.rot_dim / 2, kvh, bs, kvd, b, s))
-        return fail("mrs_dec_qkv refused the layer");
+      if (qkv_phase(bl, b, s)) return fail("q / k / v phase refused the layer");
       // one launch: splits + last-arriver merge; even GQA groups hand o_proj the Q8_K image of the result (Q8_0 weights take Q8_0 activations: f32 result)
       const bool want_img = bl.dout.type != 8 && (cfg.num_heads / kvh) % 2 == 0 && mrs_dec_act_image_bytes(nq, b) <= mrs_dec_proj_img_max_bytes();
       const int rc2 = mrs_dec_attention(want_img ? nullptr : ws.attn, want_img ? ws.attn_img : nullptr, ws.attn_ticket, (float *)ws.attn_ws, ws.max_logits, ws.exp_sums, ws.q,
                                         bl.key_cache, bl.value_cache, kvh, 1.0f / sqrtf((float)hd), bufs.block_tables, bufs.context_lens, bs, eff_max, b, cfg.num_heads, hd,
                                         cfg.max_blocks_per_seq, nq, kvh * hd * bs, hd * bs, kvd, cfg.sliding_window, s);
       if (rc2 < 0) return fail("mrs_dec_attention refused the shape");
-      // TP: h <- h / world + W_o . attn on every rank, then ONE sum all-reduce of h (the residual add stays fused, as in forward_fused)
-      const int prc = rc2 == 1 ? (mm_ok(qi_of(bl.o_proj), bl.dout.type, nq) ? mrs_dec_mm_proj(qi_of(bl.o_proj), bl.dout.type, d, nq, ws.attn_img, ws.h, d, 1, rs, b, s)
-                                                                              : mrs_dec_proj_img(&bl.dout, d, ws.attn_img, ws.h, d, 1, rs, b, s))
-                               : mrs_dec_proj(&bl.dout, d, nullptr, ws.attn, nq, nullptr, 0.f, ws.h, d, 1, rs, nullptr, b, s);
+      // TP: h <- h / world + W_o . attn on every rank, then ONE sum all-reduce of h (the residual add stays fused, as in forward_fused).  An f32 attention result (odd GQA
+      // groups, Q8_0 o_proj) is quantized inside the GEMV at every batch size.
+      const Lin o = lin(bl.dout, bl.o_proj, nq);
+      const int prc = rc2 == 1 ? proj_phase(o, d, nullptr, nullptr, ws.attn_img, ws.h, 1, rs, b, s, route(o, b)) : proj_phase(o, d, ws.attn, nullptr, nullptr, ws.h, 1, rs, b, s, R_INLINE);
       if (prc || all_reduce(ws.h, (size_t)b * d, s)) return fail("o_proj failed (%d): %s", prc, g_last_error.c_str());
       if (cfg.num_experts > 0) {
         // SparseMoeBlock::forward (models/mixtral.rs:280-304): router on the normed hidden state; per token the top-k experts' gate/up then down,
@@ -503,24 +549,14 @@ class Llama {
         if (all_reduce(ws.h, (size_t)b * d, s)) return fail("moe all-reduce failed: %s", g_last_error.c_str());
         continue;
       }
-      if (imgb) {
-        const bool mmg = mm_ok(qi_of(bl.gate_proj), bl.dgate.type, d) && qi_of(bl.up_proj);
-        if (image(ws.h, d, bl.post_attention_layernorm, d, bl.dgate.type) ||
-            (mmg ? mrs_dec_mm_gate_up(qi_of(bl.gate_proj), qi_of(bl.up_proj), bl.dgate.type, ff, d, ws.act_img, 0, ws.act, ff, b, s)
-                 : mrs_dec_gate_up_img(&bl.dgate, &bl.dup, ff, ws.act_img, 0, ws.act, ff, b, s)))
-          return fail("mrs_dec_gate_up_img refused");
-      } else if (mrs_dec_gate_up(&bl.dgate, &bl.dup, ff, nullptr, ws.h, d, bl.post_attention_layernorm, cfg.rms_eps, 0, ws.act, ff, b, s)) return fail("mrs_dec_gate_up refused");
-      const int drc = imgb ? (image(ws.act, ff, nullptr, ff, bl.ddown.type) ||
-                              (mm_ok(qi_of(bl.down_proj), bl.ddown.type, ff) ? mrs_dec_mm_proj(qi_of(bl.down_proj), bl.ddown.type, d, ff, ws.act_img, ws.h, d, 1, rs, b, s)
-                                                                               : mrs_dec_proj_img(&bl.ddown, d, ws.act_img, ws.h, d, 1, rs, b, s)))
-                                                    : mrs_dec_proj(&bl.ddown, d, nullptr, ws.act, ff, nullptr, 0.f, ws.h, d, 1, rs, nullptr, b, s);
-      if (drc || all_reduce(ws.h, (size_t)b * d, s)) return fail("down_proj failed: %s", g_last_error.c_str());
+      if (gate_up_phase(bl, b, s)) return fail("gate / up phase refused");
+      const Lin dn = lin(bl.ddown, bl.down_proj, ff);
+      if (proj_phase(dn, d, ws.act, nullptr, nullptr, ws.h, 1, rs, b, s, route(dn, b)) || all_reduce(ws.h, (size_t)b * d, s))
+        return fail("down_proj failed: %s", g_last_error.c_str());
     }
-    const int lrc = chained ? mrs_dec_proj_argmax(&dlm_head, cfg.vocab_size, ws.h, d, ln_f, cfg.rms_eps, bufs.logits, cfg.vocab_size, ws.sample_scratch, s)
-                    : imgb ? (image(ws.h, d, ln_f, d, dlm_head.type) ||
-                              (mm_ok(qi_of(lm_head), dlm_head.type, d) ? mrs_dec_mm_proj(qi_of(lm_head), dlm_head.type, cfg.vocab_size, d, ws.act_img, bufs.logits, cfg.vocab_size, 0, 1.0f, b, s)
-                                                                        : mrs_dec_proj_img(&dlm_head, cfg.vocab_size, ws.act_img, bufs.logits, cfg.vocab_size, 0, 1.0f, b, s)))
-                           : mrs_dec_proj(&dlm_head, cfg.vocab_size, nullptr, ws.h, d, ln_f, cfg.rms_eps, bufs.logits, cfg.vocab_size, 0, 1.0f, nullptr, b, s);
+    const Lin lm = lin(dlm_head, lm_head, d);
+    const int lrc = chained ? mrs_dec_proj_argmax(lm.mat, cfg.vocab_size, ws.h, d, ln_f, cfg.rms_eps, bufs.logits, cfg.vocab_size, ws.sample_scratch, s)
+                            : proj_phase(lm, cfg.vocab_size, ws.h, ln_f, nullptr, bufs.logits, 0, 1.0f, b, s, route(lm, b));
     if (lrc) return fail("lm_head refused");
     return 0;
   }

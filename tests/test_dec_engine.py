@@ -340,6 +340,13 @@ def test_image_entry_points_refuse_what_they_cannot_do_host_emulation(oracle):
     cs = be.buf(np.ones((4, hd // 2), np.float32))
     assert be.sym("mrs_dec_qkv", QKV, C.c_int)(C.byref(mq), C.byref(mq), C.byref(mq), x.ptr, k, nw.ptr, 1e-5, qb.ptr, kc.ptr, vc.ptr, sb.ptr, pb.ptr, cs.ptr, cs.ptr, hd, hd // 2,
                                                heads, 32, 1, 1, be.stream) == -1
+    # no rotated pair (head size 128): the epilogue's factor lookup clamps its index to rot_pairs - 1; refused like the matrix-core route does
+    hd = 128
+    kq, mq = repack(be, O, t, _weights(O, t, heads * hd, k, 3), heads * hd, k)
+    qb = be.buf(np.zeros((1, heads * hd), np.float32))
+    kc, vc = be.buf(np.zeros((2, heads, hd // 8, 32, 8), np.uint16)), be.buf(np.zeros((2, heads, hd, 32), np.uint16))
+    assert be.sym("mrs_dec_qkv", QKV, C.c_int)(C.byref(mq), C.byref(mq), C.byref(mq), x.ptr, k, nw.ptr, 1e-5, qb.ptr, kc.ptr, vc.ptr, sb.ptr, pb.ptr, cs.ptr, cs.ptr, hd, 0,
+                                               heads, 32, 1, 1, be.stream) == -1
 
 
 @pytest.mark.gpu

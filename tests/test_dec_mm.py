@@ -25,7 +25,7 @@ def qi_repack(be, t, packed, n, k):
     return dst
 
 
-def check_mm_proj(O, be, tname, n, k, b, norm, mode=1):
+def check_mm_proj(O, be, tname, n, k, b, norm, mode=1, resid_scale=0.5):
     t = getattr(O, tname)
     packed = _weights(O, t, n, k, 61)
     keep, m = repack(be, O, t, packed, n, k)
@@ -39,14 +39,14 @@ def check_mm_proj(O, be, tname, n, k, b, norm, mode=1):
     o1, o2 = be.buf(base.copy()), be.buf(base.copy())
     img = _act_image(be, t, xb, nb, k, b)
     assert be.sym("mrs_dec_mm_supported", [C.c_int, C.c_int, C.c_int], C.c_int)(t, k, b) == 1
-    assert be.sym("mrs_dec_proj_img", PROJ_IMG_, C.c_int)(C.byref(m), n, img.ptr, o1.ptr, n, mode, 0.5, b, be.stream) == 0
-    assert be.sym("mrs_dec_mm_proj", MM_PROJ, C.c_int)(qi.ptr, t, n, k, img.ptr, o2.ptr, n, mode, 0.5, b, be.stream) == 0
+    assert be.sym("mrs_dec_proj_img", PROJ_IMG_, C.c_int)(C.byref(m), n, img.ptr, o1.ptr, n, mode, resid_scale, b, be.stream) == 0
+    assert be.sym("mrs_dec_mm_proj", MM_PROJ, C.c_int)(qi.ptr, t, n, k, img.ptr, o2.ptr, n, mode, resid_scale, b, be.stream) == 0
     a1, a2 = o1.numpy(), o2.numpy()
     assert np.array_equal(a1, a2), (tname, n, k, b, norm, float(np.abs(a1 - a2).max()))
     xe = O.rms_norm_engine(x, nw, 1e-5) if norm else x
     eng = np.concatenate([O.gemv_engine(t, packed, n, k, r) for r in xe], axis=0)
     if mode:
-        eng = base * np.float32(0.5) + eng * np.float32(1.0)
+        eng = base * np.float32(resid_scale) + eng * np.float32(1.0)
     assert np.array_equal(a2, eng), (tname, n, k, b, norm, "engine-order oracle")
 
 
@@ -110,6 +110,12 @@ def test_mm_proj_host_emulation(oracle, tname, n, k, b, norm):
     check_mm_proj(oracle, HostBackend(), tname, n, k, b, norm)  # (n = 33 / 40 / 16: a ragged last panel; k = 768: runs of one superblock, the fourth empty; k = 256: three empty runs)
 
 
+def test_mm_proj_odd_resid_scale_host_emulation(oracle):
+    """resid_scale = 1/3 (not a power of two: the product rounds): both routes and the oracle's old * f32(rs) + sum * f32(1) agree because the RESID expression is one
+    function (csrc/dec_epilogue.cuh resid_fold)"""
+    check_mm_proj(oracle, HostBackend(), "Q4_K", 40, 1024, 3, True, resid_scale=1.0 / 3.0)
+
+
 def test_mm_store_gate_up_qkv_host_emulation(oracle):
     be = HostBackend()
     check_mm_proj(oracle, be, "Q6_K", 96, 512, 2, True, mode=0)
@@ -139,6 +145,10 @@ def test_mm_entry_points_refuse_what_they_cannot_do_host_emulation(oracle):
     # gate / up of different reduction formats share no activation image; q / k / v must agree on it too
     assert be.sym("mrs_dec_mm_qkv", MM_QKV, C.c_int)(qi.ptr, t, n, qi.ptr, t, n, qi.ptr, O.Q8_0, n, k, img.ptr, out.ptr, out.ptr, out.ptr, out.ptr, out.ptr, out.ptr, out.ptr,
                                                       128, 64, 1, 32, 1, b, be.stream) == -1
+    # no rotated pair (one activation format this time): the factor lookup clamps its index to rot_pairs - 1
+    for rot_pairs in (0, -1):
+        assert be.sym("mrs_dec_mm_qkv", MM_QKV, C.c_int)(qi.ptr, t, n, qi.ptr, t, n, qi.ptr, t, n, k, img.ptr, out.ptr, out.ptr, out.ptr, out.ptr, out.ptr, out.ptr, out.ptr,
+                                                          128, rot_pairs, 1, 32, 1, b, be.stream) == -1
 
 
 @pytest.mark.gpu
@@ -146,6 +156,11 @@ def test_mm_entry_points_refuse_what_they_cannot_do_host_emulation(oracle):
                                               ("Q5_K", 1000, 4096, 3, True), ("Q8_0", 1024, 4096, 8, True), ("Q4_K", 512, 28672, 4, False), ("Q4_K", 4096, 4096, 1, True)])
 def test_mm_proj_gpu(oracle, dev, tname, n, k, b, norm):
     check_mm_proj(oracle, GpuBackend(dev), tname, n, k, b, norm)
+
+
+@pytest.mark.gpu
+def test_mm_proj_odd_resid_scale_gpu(oracle, dev):
+    check_mm_proj(oracle, GpuBackend(dev), "Q4_K", 40, 1024, 3, True, resid_scale=1.0 / 3.0)
 
 
 @pytest.mark.gpu
