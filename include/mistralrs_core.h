@@ -76,6 +76,17 @@ void top1_large_f32_packed_batched(const float *input, float *block_values, uint
 void categorical_large_f32_packed_batched(const float *input, const float *inv_temperatures, const float *uniforms, float *block_values, float *block_sums,
                                           float *packed_out, int nrows, int ncols, int chunk_size, int nblocks, int64_t stream);
 
+/* Top-p / min-p sampling over the WHOLE row, no top-k (this library's own symbol: the reference leaves the device here, sampler.rs:649-655, 1605-1662).  One draw per
+ * row from softmax(x * inv_temperatures[row]) restricted to the kept set: top-p keeps every logit >= x*, the largest logit at which the mass of the strictly greater
+ * logits is still below top_ps[row] * total (ALL logits tied at x* are kept); min-p keeps the tokens whose weight relative to the largest exceeds min_ps[row]; a cut value
+ * outside (0, 1), NaN included, is inactive.  The cumulative kept mass is inverted in token order at uniforms[row] in [0, 1).  Masses are fixed-point integers
+ * (weight * 2^39, truncated), so the result is bit-identical across launches, batch rows and neighbours.  Workspaces block_values / block_sums [nrows][nblocks] as for
+ * categorical_large_f32_packed_batched; packed_out [nrows][4] = token id as f32, its log-probability under the FULL softmax, x* (-inf without top-p), kept mass / total
+ * mass.  An unusable row (see the categorical entry) reports four NaNs.  Returns without launching on the shapes the categorical entry refuses. */
+void mrs_nucleus_large_f32_packed_batched(const float *input, const float *inv_temperatures, const float *uniforms, const float *top_ps, const float *min_ps,
+                                          float *block_values, float *block_sums, float *packed_out, int nrows, int ncols, int chunk_size, int nblocks,
+                                          int64_t stream);
+
 /* Sampler pre-processing: dst [n] = x [n] (f32), then for the n_tokens listed token ids (ids >= n ignored): penalties -- skipped where count <= 0;
  * v -= count * frequency_penalty + presence_penalty; if repetition_penalty != 1: v = v > 0 ? v / rp : v * rp -- or additive biases.
  * replaces mistralrs-core/src/cuda/sort.cu:8-110 ; ffi.rs:45-65 ; callers sampler.rs:1113-1169 */

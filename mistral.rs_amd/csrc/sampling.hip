@@ -594,6 +594,238 @@ static void run_categorical(const float *input, const float *inv_temperatures, c
   hipLaunchKernelGGL(cat_stage2_kernel, dim3(nrows), dim3(NT), 0, s, a);
 }
 
+// ---------------------------------------------------------------- top-p / min-p over the whole row: mrs_nucleus_large_f32_packed_batched (no reference counterpart:
+// with top-k unset and a cut active the reference leaves the device, sampler.rs:649-655, and sorts the whole vocabulary on the host, sampler.rs:1605-1662).
+// stage 1 is cat_stage1_kernel as it is, so denom is the categorical denom.  stage 2, one workgroup of 1024 threads per row:
+//   gmax, denom (chunk order, thread 0) and the row's validity as in cat_stage2_kernel;
+//   every mass after that is a FIXED-POINT INTEGER, q_i = (u64)(expf(x_i * invT - gmax) * 2^39): integer adds are exact in any order, so the histogram below may use
+//   LDS atomics, and x*, the kept mass and the drawn token are functions of the row's f32 weights alone -- bit-identical whatever the launch, the batch row or the
+//   neighbours are.  (2^39, not 2^40: 2^24 tokens of weight 1 sum to 2^63 and cannot wrap; the largest weight is exactly 1 under -ffp-contract=off and 1 to within rounding otherwise.  The truncation costs at most ncols * 2^-39 of absolute mass.)
+//   top-p: x* = the logit at which the mass of the strictly greater logits first stays below top_p * Q (Q = sum q_i), found by a radix select over the
+//   order-preserving 32-bit key of the logit, 4 passes of 8 bits: a pass streams the row, adds q_i of the tokens that match the prefix into its wave's own 256-bin
+//   histogram (16 copies, 32 KiB), the copies are summed, and wave 0 walks the bins from the top (4 bins per lane + a lane scan) to the bin where the cumulative mass
+//   reaches the cutoff.  All logits equal to x* are kept (the reference keeps those its unstable sort puts first).  min-p: w_i > min_p on the f32 weight.
+//   draw: one pass for the kept mass of each wave's 1/16 of the row, then the 1024 threads share the segment that holds target = min((u64)(u * K), K - 1):
+//   contiguous runs per thread, an integer scan, the lowest kept token whose inclusive cumulative mass exceeds the target.  K > target, so a token always exists.
+// No barrier sits inside a per-token loop; no float is added in an order the hardware picks.
+struct NucArgs {
+  const float *input, *inv_temperatures, *uniforms, *top_ps, *min_ps;
+  const float *block_values, *block_sums;
+  float *packed_out;  // [rows][4] = token, logprob under the full softmax, x* (-inf without top-p), kept mass / total mass
+  int ncols, chunk_size, nblocks;
+};
+constexpr int NUC_NT = 1024, NUC_WAVES = NUC_NT / 64, NUC_UNROLL = 8;
+typedef unsigned long long u64;
+
+__device__ __forceinline__ unsigned order_key(float v) {  // a > b <=> order_key(a) > order_key(b), with -0.0 == +0.0; NaN never gets here
+  const unsigned u = __float_as_uint(v + 0.0f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float order_key_value(unsigned o) { return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o); }
+__device__ __forceinline__ u64 fixed_mass(float w) { return (u64)(w * 549755813888.0f); }  // 2^39: the product is exact, the conversion truncates
+__device__ __forceinline__ u64 wave_sum_u64(u64 v) {
+#pragma unroll
+  for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
+__device__ __forceinline__ u64 wave_scan_u64(u64 v) {  // inclusive
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const u64 o = __shfl(v, (lane - d) & 63, 64);
+    if (lane >= d) v += o;
+  }
+  return v;
+}
+
+__global__ void __launch_bounds__(NUC_NT) nuc_stage2_kernel(NucArgs a) {
+  __shared__ u64 s_hist[NUC_WAVES][256];
+  __shared__ float s_cum[CAT_MAXB];
+  __shared__ float s_wmax[NUC_WAVES];
+  __shared__ int s_wnan[NUC_WAVES];
+  __shared__ u64 s_wkept[NUC_WAVES], s_wall[NUC_WAVES], s_wscan[NUC_WAVES];
+  __shared__ float s_denom;
+  __shared__ int s_ok, s_digit;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nb = a.nblocks, n = a.ncols;
+  const size_t row = blockIdx.x;
+  const float *input = a.input + row * (size_t)n;
+  const float *bv = a.block_values + row * (size_t)nb, *bs = a.block_sums + row * (size_t)nb;
+  float *packed = a.packed_out + row * 4;
+  const float inv_t = a.inv_temperatures[row], top_p = a.top_ps[row], min_p = a.min_ps[row];
+  const bool cut_p = top_p > 0.0f && top_p < 1.0f, cut_m = min_p > 0.0f && min_p < 1.0f;  // NaN: no cut
+  // ---- gmax, denom, validity: cat_stage2_kernel's, on 16 waves
+  float m = -INFINITY;
+  bool nan = false;
+  for (int b = tid; b < nb; b += NUC_NT) {
+    const float c = bv[b];
+    if (c != c) nan = true;
+    else m = fmaxf(m, c);
+  }
+  m = wave_max(m);
+  const bool wave_nan = __ballot(nan) != 0ull;
+  if (lane == 0) { s_wmax[wave] = m; s_wnan[wave] = wave_nan ? 1 : 0; }
+  __syncthreads();
+  bool any_nan = false;
+  float rmax = -INFINITY;
+  for (int i = 0; i < NUC_WAVES; ++i) { any_nan = any_nan || s_wnan[i] != 0; rmax = fmaxf(rmax, s_wmax[i]); }
+  const float gmax = any_nan ? NAN : rmax * inv_t;
+  auto mass = [&](int b) { return bs[b] * expf(bv[b] * inv_t - gmax); };
+  for (int b = tid; b < nb && b < CAT_MAXB; b += NUC_NT) s_cum[b] = mass(b);
+  __syncthreads();
+  if (tid == 0) {
+    float cum = 0.0f;
+    for (int b = 0; b < nb; ++b) cum += b < CAT_MAXB ? s_cum[b] : mass(b);
+    const float u = a.uniforms[row];
+    const bool ok = inv_t > 0.0f && finite_f32(inv_t) && u >= 0.0f && u < 1.0f && finite_f32(gmax) && cum > 0.0f && finite_f32(cum);
+    s_denom = cum;
+    s_ok = ok ? 1 : 0;
+    if (!ok) { packed[0] = NAN; packed[1] = NAN; packed[2] = NAN; packed[3] = NAN; }
+  }
+  __syncthreads();
+  if (!s_ok) return;
+  auto weight = [&](float x) { return expf(x * inv_t - gmax); };
+  // ---- top-p: the threshold key, 8 bits a pass from the top
+  unsigned kstar = 0u;  // every key is >= 0: no top-p cut
+  double cut = 0.0;
+  u64 above = 0ull;
+  if (cut_p) {
+    for (int pass = 0; pass < 4; ++pass) {
+      const int shift = 24 - 8 * pass;
+      for (int i = tid; i < NUC_WAVES * 256; i += NUC_NT) (&s_hist[0][0])[i] = 0ull;
+      __syncthreads();
+      for (long long base = tid; base < n; base += NUC_UNROLL * NUC_NT) {  // NUC_UNROLL loads in flight: one workgroup streams the row, and a load is a trip to L2
+        float xs[NUC_UNROLL];
+#pragma unroll
+        for (int j = 0; j < NUC_UNROLL; ++j) {
+          const long long i = base + (long long)j * NUC_NT;
+          xs[j] = i < n ? input[i] : 0.0f;
+        }
+#pragma unroll
+        for (int j = 0; j < NUC_UNROLL; ++j) {
+          const unsigned key = order_key(xs[j]);
+          if (base + (long long)j * NUC_NT < n && (pass == 0 || (key >> (shift + 8)) == (kstar >> (shift + 8)))) {
+            const u64 q = fixed_mass(weight(xs[j]));
+            if (q != 0ull) atomicAdd(&s_hist[wave][(key >> shift) & 255u], q);
+          }
+        }
+      }
+      __syncthreads();
+      if (tid < 256) {
+        u64 t = 0ull;
+        for (int w = 0; w < NUC_WAVES; ++w) t += s_hist[w][tid];
+        s_hist[0][tid] = t;  // only this thread reads or writes column `tid`
+      }
+      __syncthreads();
+      if (wave == 0) {  // lane l owns the bins 255 - 4l .. 252 - 4l, walked downwards; `cut` and `above` live in wave 0's registers across the passes
+        u64 t[4], local = 0ull;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { t[j] = s_hist[0][255 - 4 * lane - j]; local += t[j]; }
+        const u64 incl = wave_scan_u64(local);
+        if (pass == 0) cut = (double)top_p * (double)__shfl(incl, 63, 64);  // top_p * Q, Q = the row's whole mass; > 0: the arg-max alone weighs about 2^39
+        u64 cum = above + (incl - local);
+        int hit = -1;
+        u64 hit_above = 0ull;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          if (hit < 0 && t[j] != 0ull && (double)(cum + t[j]) >= cut) { hit = 255 - 4 * lane - j; hit_above = cum; }
+          cum += t[j];
+        }
+        const unsigned long long hits = __ballot(hit >= 0);
+        const int first_lane = hits ? __ffsll((long long)hits) - 1 : 0;
+        above = __shfl(hit_above, first_lane, 64);  // the mass strictly above the chosen bin: stays below the cutoff
+        const int digit = __shfl(hit, first_lane, 64);
+        if (lane == 0) s_digit = hits ? digit : -1;
+      }
+      __syncthreads();
+      const int digit = s_digit;
+      if (digit < 0) {  // unreachable: the cumulative mass ends at the bin mass the previous pass selected, which had reached the cutoff
+        if (tid == 0) { packed[0] = NAN; packed[1] = NAN; packed[2] = NAN; packed[3] = NAN; }
+        return;
+      }
+      kstar |= (unsigned)digit << shift;
+    }
+  }
+  // ---- kept mass and total mass of each wave's sixteenth of the row
+  auto kept_mass = [&](float x) -> u64 {
+    const float w = weight(x);
+    return (order_key(x) >= kstar && (!cut_m || w > min_p)) ? fixed_mass(w) : 0ull;
+  };
+  const long long seg = ((long long)n + NUC_WAVES - 1) / NUC_WAVES;
+  {
+    const long long lo = wave * seg, hi = lo + seg < n ? lo + seg : n;
+    u64 kq = 0ull, tq = 0ull;
+    for (long long base = lo + lane; base < hi; base += NUC_UNROLL * 64) {
+      float xs[NUC_UNROLL];
+#pragma unroll
+      for (int j = 0; j < NUC_UNROLL; ++j) {
+        const long long i = base + j * 64;
+        xs[j] = i < hi ? input[i] : 0.0f;
+      }
+#pragma unroll
+      for (int j = 0; j < NUC_UNROLL; ++j) {
+        if (base + j * 64 < hi) {
+          const float w = weight(xs[j]);
+          const u64 q = fixed_mass(w);
+          tq += q;
+          if (order_key(xs[j]) >= kstar && (!cut_m || w > min_p)) kq += q;
+        }
+      }
+    }
+    kq = wave_sum_u64(kq);
+    tq = wave_sum_u64(tq);
+    if (lane == 0) { s_wkept[wave] = kq; s_wall[wave] = tq; }
+  }
+  __syncthreads();
+  u64 kept = 0ull, all = 0ull, before = 0ull;
+  for (int w = 0; w < NUC_WAVES; ++w) { kept += s_wkept[w]; all += s_wall[w]; }
+  if (kept == 0ull) {  // unreachable: the arg-max has weight 1 (to within rounding in a contracted build) and passes both cuts
+    if (tid == 0) { packed[0] = NAN; packed[1] = NAN; packed[2] = NAN; packed[3] = NAN; }
+    return;
+  }
+  u64 target = (u64)((double)a.uniforms[row] * (double)kept);
+  if (target >= kept) target = kept - 1ull;
+  int sel = NUC_WAVES - 1;
+  for (int w = 0; w < NUC_WAVES; ++w) {
+    if (before + s_wkept[w] > target) { sel = w; break; }
+    before += s_wkept[w];
+  }
+  target -= before;  // < s_wkept[sel]
+  // ---- the selected sixteenth: thread t owns the tokens [lo + t * per, lo + t * per + per)
+  const long long lo = sel * seg, hi = lo + seg < n ? lo + seg : n;
+  const long long per = (seg + NUC_NT - 1) / NUC_NT, first = lo + tid * per, last = first + per < hi ? first + per : hi;
+  u64 mine = 0ull;
+  for (long long i = first; i < last; ++i) mine += kept_mass(input[i]);
+  const u64 incl = wave_scan_u64(mine);
+  if (lane == 63) s_wscan[wave] = incl;
+  __syncthreads();
+  u64 run = incl - mine;
+  for (int w = 0; w < wave; ++w) run += s_wscan[w];
+  // the lowest kept token whose inclusive cumulative mass exceeds the target: a token of mass 0 never moves the sum and is never returned
+  long long hit = -1;
+  if (run <= target && run + mine > target)
+    for (long long i = first; i < last && hit < 0; ++i) {
+      run += kept_mass(input[i]);
+      if (run > target) hit = i;
+    }
+  if (hit >= 0) {  // exactly one thread of the workgroup holds the crossing: 0 <= target < the segment's kept mass, all integers
+    const float x = input[hit];
+    packed[0] = (float)hit;
+    packed[1] = x * inv_t - gmax - logf(s_denom);
+    packed[2] = cut_p ? order_key_value(kstar) : -INFINITY;
+    packed[3] = (float)((double)kept / (double)all);
+  }
+}
+
+static void run_nucleus(const float *input, const float *inv_temperatures, const float *uniforms, const float *top_ps, const float *min_ps, float *block_values,
+                        float *block_sums, float *packed_out, int nrows, int ncols, int chunk_size, int nblocks, int64_t stream) {
+  if (nrows < 1 || ncols < 1 || chunk_size < 1 || chunk_size > NT * MAXV || (long long)nblocks * chunk_size < ncols) return;  // run_categorical's refusals
+  hipStream_t s = (hipStream_t)stream;
+  CatArgs a1{input, inv_temperatures, uniforms, block_values, block_sums, nullptr, ncols, chunk_size, nblocks};
+  NucArgs a2{input, inv_temperatures, uniforms, top_ps, min_ps, block_values, block_sums, packed_out, ncols, chunk_size, nblocks};
+  hipLaunchKernelGGL(cat_stage1_kernel, dim3(nblocks, nrows), dim3(NT), 0, s, a1);
+  hipLaunchKernelGGL(nuc_stage2_kernel, dim3(nrows), dim3(NUC_NT), 0, s, a2);
+}
+
 // ---------------------------------------------------------------- logits pre-processing of the sampler (sort.cu:8-110; callers sampler.rs:1113-1169)
 // dst = x, then the listed tokens are updated in place: penalties (frequency / presence / repetition, counts from the context) or additive biases.
 __global__ void __launch_bounds__(NT) copy_f32_kernel(const float *__restrict__ x, float *__restrict__ dst, int n) {
@@ -654,6 +886,11 @@ extern "C" void top1_large_f32_packed_batched(const float *input, float *block_v
 extern "C" void categorical_large_f32_packed_batched(const float *input, const float *inv_temperatures, const float *uniforms, float *block_values, float *block_sums,
                                                      float *packed_out, int nrows, int ncols, int chunk_size, int nblocks, int64_t stream) {
   mrs::sampling::run_categorical(input, inv_temperatures, uniforms, block_values, block_sums, packed_out, nrows, ncols, chunk_size, nblocks, stream);
+}
+extern "C" void mrs_nucleus_large_f32_packed_batched(const float *input, const float *inv_temperatures, const float *uniforms, const float *top_ps, const float *min_ps,
+                                                     float *block_values, float *block_sums, float *packed_out, int nrows, int ncols, int chunk_size, int nblocks,
+                                                     int64_t stream) {
+  mrs::sampling::run_nucleus(input, inv_temperatures, uniforms, top_ps, min_ps, block_values, block_sums, packed_out, nrows, ncols, chunk_size, nblocks, stream);
 }
 extern "C" void apply_sparse_penalties_f32(const void *x, void *dst, const uint32_t *token_ids, const float *counts, const int n, const int n_tokens,
                                            const float frequency_penalty, const float presence_penalty, const float repetition_penalty, int64_t stream) {

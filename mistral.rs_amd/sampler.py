@@ -213,18 +213,124 @@ def categorical_host(logits_row, inv_temperature, uniform):
     return tok, float(np.float32(np.float32(x[tok] * inv_t - gmax) - np.log(denom, dtype=np.float32)))
 
 
-def generate(model, prompt, max_new_tokens: int, top_k: int, temperature: float = 1.0, top_p: float = 1.0, min_p: float = 0.0, seed: int = 0):
+class Nucleus:
+    """Workspace + launcher of the device top-p / min-p draw over rows of `vocab` f32 logits (`mrs_nucleus_large_f32_packed_batched`; the reference has no device path
+    for this case, sampler.rs:649-655).  Per-row temperature, uniform, top_p and min_p; a cut outside (0, 1) is inactive."""
+
+    def __init__(self, vocab: int, device, max_rows: int = 1):
+        vocab, max_rows = int(vocab), int(max_rows)
+        if vocab <= 0:
+            raise ValueError("nucleus: empty logits")
+        if vocab > 2 ** 24:
+            raise ValueError(f"nucleus: vocab={vocab} exceeds 2**24 (token ids come back as f32)")
+        if max_rows < 1 or max_rows > 65535:
+            raise ValueError(f"nucleus: max_rows={max_rows} must be in [1, 65535]")
+        self.vocab, self.max_rows, self.device = vocab, max_rows, device
+        self.nblocks = (vocab + CHUNK_SIZE - 1) // CHUNK_SIZE
+        f32 = dict(dtype=torch.float32, device=device)
+        self.block_values = torch.empty(max_rows, self.nblocks, **f32)
+        self.block_sums = torch.empty(max_rows, self.nblocks, **f32)
+        self.packed = torch.empty(max_rows, 4, **f32)
+        self._params = torch.empty(4, max_rows, **f32)  # inverse temperatures, uniforms, top_p, min_p: one upload
+        vp, i, ll = C.c_void_p, C.c_int, C.c_int64
+        self._many = _lib.sym("core", "mrs_nucleus_large_f32_packed_batched", [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, ll])
+
+    def __call__(self, logits: torch.Tensor, temperature, uniforms, top_p=1.0, min_p=0.0) -> torch.Tensor:
+        """logits f32 [vocab] or [rows, vocab] (contiguous, on the device); temperature: positive and finite; uniforms: one value in [0, 1) per row; top_p / min_p: a
+        float or one per row.  Returns the packed rows [rows, 4] = (token id, logprob under the full softmax, threshold logit x*, kept share of the mass) on the
+        device (a view of this object's buffer: consume it before the next call)."""
+        x = logits.reshape(-1, self.vocab) if logits.dim() > 1 else logits.reshape(1, self.vocab)
+        rows = x.shape[0]
+        if x.dtype != torch.float32 or not x.is_contiguous() or rows > self.max_rows:
+            raise ValueError("nucleus: logits must be contiguous f32 with at most max_rows rows")
+        temps = np.broadcast_to(np.asarray(temperature, dtype=np.float64), (rows,))
+        if not np.all(np.isfinite(temps) & (temps > 0)):
+            raise ValueError("nucleus requires a positive finite temperature")
+        u = np.asarray(uniforms, dtype=np.float32).reshape(-1)
+        if u.shape[0] != rows or not np.all((u >= 0) & (u < 1)):
+            raise ValueError("nucleus requires one uniform in [0, 1) per row")
+        tp = np.broadcast_to(np.asarray(top_p, dtype=np.float32), (rows,))
+        mp = np.broadcast_to(np.asarray(min_p, dtype=np.float32), (rows,))
+        params = np.stack([(1.0 / temps).astype(np.float32), u, tp, mp])
+        self._params[:, :rows].copy_(torch.from_numpy(params), non_blocking=False)
+        pr = [self._params[j].data_ptr() for j in range(4)]
+        self._many(x.data_ptr(), pr[0], pr[1], pr[2], pr[3], self.block_values.data_ptr(), self.block_sums.data_ptr(), self.packed.data_ptr(), rows, self.vocab,
+                   CHUNK_SIZE, self.nblocks, torch.cuda.current_stream().cuda_stream)
+        return self.packed[:rows]
+
+
+def nucleus_token(packed4):
+    """(token, logprob) of one packed row of the nucleus draw; raises on an unusable row (four NaNs), like `categorical_token`"""
+    tok, lp = float(packed4[0]), float(packed4[1])
+    if not (np.isfinite(tok) and np.isfinite(lp)) or tok < 0 or tok != np.floor(tok) or np.isnan(packed4[2]) or np.isnan(packed4[3]):
+        raise ValueError("invalid batched nucleus output")
+    return int(tok), lp
+
+
+def cut_active(v) -> bool:
+    """a top_p / min_p value cuts iff it lies strictly inside (0, 1) (sampler.rs:1625, 1645); None, NaN and everything else: no cut"""
+    return v is not None and 0.0 < float(v) < 1.0
+
+
+NUCLEUS_SCALE = 2.0 ** 39  # the fixed-point unit of csrc/sampling.hip: masses are integers, so their sums do not depend on the order of addition
+
+
+def nucleus_host(logits_row, inv_temperature, uniform, top_p=1.0, min_p=0.0):
+    """The contract of `mrs_nucleus_large_f32_packed_batched` for one row in numpy: (token, logprob, x*, kept share).  f32 weights, integer masses
+    q_i = floor(w_i * 2^39); top-p keeps every logit >= x*, the largest logit at which the mass of the strictly greater logits is still below top_p * sum q (ALL ties
+    at x* are kept); min-p keeps w_i > min_p; the draw inverts the cumulative kept mass in token order at min(floor(u * K), K - 1).  Raises where the device reports NaNs."""
+    x, inv_t, u = np.asarray(logits_row, dtype=np.float32).reshape(-1), np.float32(inv_temperature), np.float32(uniform)
+    tp, mp = np.float32(top_p), np.float32(min_p)
+    with np.errstate(over="ignore", invalid="ignore"):
+        gmax = np.float32(x.max() * inv_t) if x.size else np.float32(np.nan)
+        ok = np.isfinite(inv_t) and inv_t > 0 and np.isfinite(u) and 0 <= u < 1 and np.isfinite(gmax)
+        if ok:
+            w = np.exp((x * inv_t - gmax).astype(np.float32), dtype=np.float32)
+            denom = w.sum(dtype=np.float32)  # numpy's pairwise f32 sum: as close to the exact sum as the device's chunked trees
+            ok = np.isfinite(denom) and denom > 0
+    if not ok:
+        raise ValueError("invalid batched nucleus output")
+    q = (w.astype(np.float64) * NUCLEUS_SCALE).astype(np.uint64)  # exact: a power-of-two scale, then truncation
+    total = int(q.sum(dtype=np.uint64))
+    keep = np.ones(x.size, dtype=bool)
+    xstar = np.float32(-np.inf)
+    if 0.0 < tp < 1.0:
+        order = np.argsort(-x, kind="stable")
+        xs, qs = x[order], q[order]
+        firsts = np.nonzero(np.r_[True, xs[1:] != xs[:-1]])[0]  # the first position of each distinct logit, descending
+        above = np.r_[np.uint64(0), np.cumsum(qs, dtype=np.uint64)][firsts]  # the mass strictly above it
+        cut = np.float64(tp) * np.float64(total)
+        at = np.add.reduceat(qs, firsts)
+        hit = np.nonzero((at > 0) & ((above + at).astype(np.float64) >= cut))[0][0]
+        xstar = xs[firsts[hit]]
+        keep &= x >= xstar
+    if 0.0 < mp < 1.0:
+        keep &= w > mp
+    cum = np.cumsum(np.where(keep, q, np.uint64(0)), dtype=np.uint64)
+    kept = int(cum[-1])
+    target = min(int(np.float64(u) * np.float64(kept)), kept - 1)
+    tok = int(np.searchsorted(cum, np.uint64(target), side="right"))
+    lp = float(np.float32(np.float32(x[tok] * inv_t - gmax) - np.log(denom, dtype=np.float32)))
+    return tok, lp, float(xstar), float(np.float32(np.float64(kept) / np.float64(total)))
+
+
+def generate(model, prompt, max_new_tokens: int, top_k: int, temperature: float = 1.0, top_p: float = 1.0, min_p: float = 0.0, seed: int = 0,
+             full_vocab_cuts: bool = False):
     """Sampled decoding on a `Llama` runner (the loop of `Sampler::sample`, sampler.rs:1262-1290): prefill, then per token one decode step and
       top_k >= 2: the device top-k over the logits row, `2k + 2` floats to the host, the top-p / min-p cuts and the draw there;
       top_k == 1: the arg-max through the top-1 kernels, no temperature, probability 1 (sample_cuda_top1_row);
       top_k <= 0 or None (top_p and min_p inactive): the device categorical draw over the whole row at `uniform_for(seed, i)` -- one launch pair, 2 floats to the host,
-                 probability exp(logprob).  With an active top_p or min_p this raises: the reference falls back to its CPU sampler there, which is not mirrored.
+                 probability exp(logprob).  With an active top_p or min_p: `full_vocab_cuts=True` draws through `Nucleus` (the cuts over the WHOLE vocabulary on the
+                 device, 4 floats to the host); without the keyword this raises, as the reference leaves the device there.
     Returns (tokens, reporting probabilities)."""
     vocab = int(model.cfg.vocab_size)
     if top_k is None or int(top_k) <= 0:
-        if 0.0 < top_p < 1.0 or 0.0 < min_p < 1.0:
+        cuts = 0.0 < top_p < 1.0 or 0.0 < min_p < 1.0
+        if cuts and not full_vocab_cuts:
             raise ValueError("sampling with top_p / min_p needs top_k >= 1 (the device categorical draw takes the whole row)")
-        k, t1, tk, cat = 0, None, None, Categorical(vocab, model.device)
+        k, t1, tk = 0, None, None
+        cat = None if cuts else Categorical(vocab, model.device)
+        nuc = Nucleus(vocab, model.device) if cuts else None
     else:
         k = min(int(top_k), vocab)
         t1 = Top1(vocab, model.device) if k == 1 else None
@@ -235,7 +341,10 @@ def generate(model, prompt, max_new_tokens: int, top_k: int, temperature: float 
     for i in range(max_new_tokens):
         if hasattr(model, "p2p_sync_error") and model.p2p_sync_error():  # tensor parallel: a timed-out peer-mailbox sum is NaN -- never hand out a token from it
             raise RuntimeError("p2p all-reduce timed out: the route has been dropped on every rank (RCCL from now on); re-run the request")
-        if k == 0:
+        if k == 0 and nuc is not None:
+            tok, lp = nucleus_token(nuc(logits.contiguous(), temperature, [uniform_for(seed, i)], top_p, min_p).cpu().numpy()[0])
+            p = min(1.0, float(np.exp(lp)))
+        elif k == 0:
             tok, lp = categorical_token(cat(logits.contiguous(), temperature, [uniform_for(seed, i)]).cpu().numpy()[0])
             p = min(1.0, float(np.exp(lp)))
         elif k == 1:  # sample_cuda_top1_row (sampler.rs:767-781): the arg-max, no temperature, logprob 0 (probability 1)

@@ -45,7 +45,9 @@ class Sequence:
     last_logits: object = None
     temperature: Optional[float] = None   # None: greedy (arg-max); else the categorical draw over the whole row at this temperature
     seed: int = 0                         # token j is drawn at sampler.uniform_for(seed, j): a recomputed sequence redraws the same tokens
-    logprobs: List[float] = field(default_factory=list)  # one entry per SAMPLED token (greedy tokens add none)
+    logprobs: List[float] = field(default_factory=list)  # one entry per SAMPLED token (greedy tokens add none): under the FULL softmax, cuts or not
+    top_p: Optional[float] = None         # a value strictly inside (0, 1) cuts the nucleus over the whole vocabulary (needs a temperature); anything else: no cut
+    min_p: Optional[float] = None
 
     def __post_init__(self):
         if not self.prompt_len:
@@ -104,6 +106,9 @@ class PagedAttentionScheduler:
 
     # ---- queue interface (Scheduler trait, scheduler.rs:1082-1110)
     def add_seq(self, seq: Sequence) -> None:
+        from .sampler import cut_active
+        if seq.temperature is None and (cut_active(seq.top_p) or cut_active(seq.min_p)):
+            raise ValueError("top_p / min_p need a temperature: a greedy sequence takes the arg-max")
         self._clock += 1
         if not seq.timestamp:
             seq.timestamp = self._clock
@@ -297,6 +302,7 @@ class PagedEngine:
         self.cfg = model.cfg
         self.steps = {"prompt": 0, "completion": 0, "preemptions": 0}
         self._cat = None  # sampler.Categorical, made at the first sampled token
+        self._nuc = None  # sampler.Nucleus, made at the first token drawn under a top_p / min_p cut
 
     def _table(self, seq: Sequence):
         import torch
@@ -312,25 +318,44 @@ class PagedEngine:
 
     def _finish_tokens(self, seqs: List[Sequence], logits) -> None:
         """The next token of every row of one launch (`logits[i]` belongs to `seqs[i]`): rows with a temperature are drawn TOGETHER -- one categorical launch pair over
-        their logits with per-row inverse temperature and uniform, one copy of 2 floats per row; greedy rows keep the arg-max.  A (NaN, NaN) pair raises.
+        their logits with per-row inverse temperature and uniform, one copy of 2 floats per row; rows with an active top_p / min_p cut go TOGETHER through one nucleus
+        launch (per-row cuts, 4 floats per row; `nucleus_host` on a CPU runner); greedy rows keep the arg-max.  A NaN row raises.
         Tensor parallel: every rank holds the same logits after the all-reduce and derives the same uniforms from (seed, position), so every rank draws the
         same token without any further communication."""
+        import torch
         from . import sampler
-        sampled = [i for i, s in enumerate(seqs) if s.temperature is not None]
+        cuts = lambda s: sampler.cut_active(s.top_p) or sampler.cut_active(s.min_p)
+        # add_seq refuses this at submission; the fields of a Sequence stay writable afterwards, and the engine is also driven without a scheduler
+        if any(s.temperature is None and cuts(s) for s in seqs):
+            raise ValueError("top_p / min_p need a temperature: a greedy sequence takes the arg-max")
+        sampled = [i for i, s in enumerate(seqs) if s.temperature is not None and not cuts(s)]
+        cut = [i for i, s in enumerate(seqs) if s.temperature is not None and cuts(s)]  # ONE nucleus launch with per-row top_p / min_p, 4 floats per row
         drawn = {}
+        pick = lambda idx: logits[idx[0]: idx[0] + 1] if len(idx) == 1 else logits[torch.tensor(idx, device=logits.device)]
         if sampled:
             us = [sampler.uniform_for(seqs[i].seed, len(seqs[i].generated)) for i in sampled]
             if self.m.device.type == "cpu":  # host runners: the same rule in numpy
                 for i, u in zip(sampled, us):
                     drawn[i] = sampler.categorical_host(logits[i].float().numpy(), np.float32(1.0 / seqs[i].temperature), u)
             else:
-                import torch
-                x = logits[sampled[0]: sampled[0] + 1] if len(sampled) == 1 else logits[torch.tensor(sampled, device=logits.device)]
                 if self._cat is None:
                     self._cat = sampler.Categorical(self.cfg.vocab_size, self.m.device, max_rows=max(8, self.cfg.max_batch))
-                packed = self._cat(x.float().contiguous(), [seqs[i].temperature for i in sampled], us).cpu().numpy()
+                packed = self._cat(pick(sampled).float().contiguous(), [seqs[i].temperature for i in sampled], us).cpu().numpy()
                 for r, i in enumerate(sampled):
                     drawn[i] = sampler.categorical_token(packed[r])
+        if cut:
+            us = [sampler.uniform_for(seqs[i].seed, len(seqs[i].generated)) for i in cut]
+            tps = [seqs[i].top_p if sampler.cut_active(seqs[i].top_p) else 1.0 for i in cut]
+            mps = [seqs[i].min_p if sampler.cut_active(seqs[i].min_p) else 0.0 for i in cut]
+            if self.m.device.type == "cpu":
+                for i, u, tp, mp in zip(cut, us, tps, mps):
+                    drawn[i] = sampler.nucleus_host(logits[i].float().numpy(), np.float32(1.0 / seqs[i].temperature), u, tp, mp)[:2]
+            else:
+                if self._nuc is None:
+                    self._nuc = sampler.Nucleus(self.cfg.vocab_size, self.m.device, max_rows=max(8, self.cfg.max_batch))
+                packed = self._nuc(pick(cut).float().contiguous(), [seqs[i].temperature for i in cut], us, tps, mps).cpu().numpy()
+                for r, i in enumerate(cut):
+                    drawn[i] = sampler.nucleus_token(packed[r])
         for i, seq in enumerate(seqs):
             if i in drawn:
                 seq.logprobs.append(drawn[i][1])
