@@ -1,23 +1,39 @@
-// sampling.hip -- libmistralrscuda, sampling subset: top-k of one logits row over a 100k+ vocabulary + the pieces of the full-softmax normaliser the host
-// sampler needs (Sampler::sample_topk_on_device, mistralrs-core/src/sampler.rs:1171-1260: with top-k set, top-p / min-p / the multinomial draw stay on the host);
-// the greedy arg-max; and the categorical draw over the WHOLE row (temperature only, no top-k: the draw itself runs on the device, see the section further down).
-//   categorical_large_f32_packed_batched                                      sort.cu:1825-2069,2240-2257 ; ffi.rs:666 ; caller ops.rs:1347-1500 (temperature sampling)
-//   top1_large_f32_packed, top1_large_f32_packed_batched                     sort.cu:1825-1912,2071-2143,2207-2238 ; ffi.rs:643-665 ; caller ops.rs:1232-2000 (greedy)
-//   topk_large_f32, topk_large_f32_packed, topk_large_f32_packed_batched      mistralrs-core/src/cuda/sort.cu:1502-1823,2146-2206 ; ffi.rs:583-624 ;
-//                                                                              caller ops.rs:691-828 (cuda_topk_logits_f32_packed)
-// Contract kept from the reference (the caller owns every buffer):
-//   stage 1, one workgroup per `chunk_size` logits: block_values / block_indices [chunk][k] = the chunk's k largest logits in (value descending, index
-//   ascending) order, NaN and -inf never selected, missing entries (-inf, 0); block_maxes[chunk] = top value * inv_temperature (-inf for an empty chunk);
-//   block_sums[chunk] = sum over the chunk of expf(x * inv_temperature - block_max) (NaN if the chunk holds one);
-//   stage 2, one workgroup per row: global max of block_maxes, denom = sum_b block_sums[b] * expf(block_maxes[b] - max), and the k best candidates in the
-//   same order; packed_out = [k values][k indices as f32][denom][max].
-// MI355X design (not the reference's k rounds of scan-the-chunk + two block barriers each):
-//   stage 1: a chunk lives in REGISTERS (<= 16 logits per thread), every wave extracts the top-k of its quarter on its own -- one 64-bit key per candidate
-//   (order-preserving float bits << 32 | ~index, so ONE max reduction per round settles value and tie; DPP + v_readlane, no LDS crossbar), each lane's keys
-//   sorted once so that its best is keys[0], no barrier -- then wave 0 merges the four sorted lists by heads (one lane per list).  stage 2 is the same head merge over the nblocks sorted lists (a lane per list, lists beyond
-//   64 share lanes): k rounds of one wave-wide max instead of k scans of nblocks * k candidates.
-//   The f32 sums keep the reference's association (per-thread strided partials, 32-lane shuffle-down trees, warp sums through LDS) so that only expf's last
-//   ulp separates the normaliser from the CUDA build's.
+// sampling.hip -- libmistralrscuda, sampling subset.  A MAP of this file: three two-stage families over rows of 100k+ f32 logits, the helpers they share, and the
+// arithmetic each helper pins.  (Further down, apart from all this: the sparse penalties / bias pre-processing.)  The caller owns every buffer.
+//
+// The families -- stage 1 is one workgroup of NT threads per `chunk_size` logits, stage 2 one workgroup per row; the row is always a block index:
+//   top-k        topk_large_f32, topk_large_f32_packed, topk_large_f32_packed_batched      mistralrs-core/src/cuda/sort.cu:1502-1823,2146-2206 ; ffi.rs:583-624 ;
+//                caller ops.rs:691-828 (cuda_topk_logits_f32_packed); top-p / min-p / the multinomial draw stay on the host (Sampler::sample_topk_on_device,
+//                mistralrs-core/src/sampler.rs:1171-1260).
+//                stage 1: block_values / block_indices [chunk][k] = the chunk's k largest logits in (value descending, index ascending) order, NaN and -inf never
+//                selected, missing entries (-inf, 0); block_maxes[chunk] = top value * inv_temperature (-inf for an empty chunk); block_sums[chunk] = the chunk's
+//                share of the normaliser.  stage 2: global max of block_maxes, denom = sum_b block_sums[b] * expf(block_maxes[b] - max), the k best candidates in
+//                the same order; packed_out = [k values][k indices as f32][denom][max].
+//   greedy       top1_large_f32_packed, top1_large_f32_packed_batched                      sort.cu:1825-1912,2071-2143,2207-2238 ; ffi.rs:643-665 ; caller ops.rs:1232-2000.
+//                No softmax: block_argmax twice.  Shares only the candidate key with the others.
+//   draws        categorical_large_f32_packed_batched (sort.cu:1825-2069,2240-2257 ; ffi.rs:666 ; caller ops.rs:1347-1500: temperature only) and
+//                mrs_nucleus_large_f32_packed_batched (top-p / min-p over the whole row; no reference counterpart).  ONE stage 1, cat_stage1_kernel: block_values =
+//                the chunk's largest raw logit (NaN if it holds one), block_sums = the chunk's share under block_value * inv_t.  Two stage 2s behind one row preamble:
+//                cat_stage2_kernel inverts f32 running sums, nuc_stage2_kernel fixed-point integer masses -- they may draw different tokens and stay apart.
+//
+// The shared helpers, and what each one pins:
+//   order_key / order_key_value    the float <-> order-preserving unsigned mapping (-0.0 == +0.0).  key_of / val_of / idx_of build the 64-bit candidate key of
+//                                  top-k and greedy on it; the nucleus radix select reads its digits from it.
+//   load_chunk                     the chunk in registers, thread-strided (local = tid + NT j).  Both stage 1s; the partial sums below depend on this assignment.
+//   chunk_softmax_share            block_sums: sum of expf(x * inv_t - block_max), NaN rule included, in the reference's association (per-thread strided partials,
+//                                  block_sum_ref_order: 32-lane shuffle-down trees, warp sums through LDS), so that only expf's last ulp separates the normaliser
+//                                  from the CUDA build's.  Both stage 1s: the three entry points leave bit-identical block_sums for the same logits and temperature.
+//   block_max_nan<WAVES>           workgroup max with a carried NaN flag: cat_stage1_kernel (4 waves) and, through the preamble, both draw stage 2s (4 and 16 waves).
+//   row_preamble<NTH>, chunk_mass  gmax, the chunk masses, denom = their sum by ONE thread in ascending chunk index, the validity expression.  Both draw stage 2s:
+//                                  the logprob of either draw is x * inv_t - gmax - logf(denom) with this gmax and this denom.
+//   store_nan_row                  the unusable-row report of both draws.      draw_shape_ok: the launch refusals of both draws.
+//   head_merge, wave_max_u64       top-k only (stage 1's merge of four wave lists, stage 2's merge of nblocks lists).      block_argmax: greedy only.
+//
+// MI355X design of top-k (not the reference's k rounds of scan-the-chunk + two block barriers each):
+//   stage 1: every wave extracts the top-k of its quarter of the register-resident chunk on its own -- one 64-bit key per candidate (order key << 32 | ~index, so ONE
+//   max reduction per round settles value and tie; DPP + v_readlane, no LDS crossbar), each lane's keys sorted once so that its best is keys[0], no barrier -- then
+//   wave 0 merges the four sorted lists by heads (one lane per list).  stage 2 is the same head merge over the nblocks sorted lists (a lane per list, lists beyond 64
+//   share lanes): k rounds of one wave-wide max instead of k scans of nblocks * k candidates.
 #include "common.cuh"
 #include <stdint.h>
 #include <algorithm>
@@ -31,19 +47,21 @@ constexpr int MAX_K = 128;    // CUDA_TOPK_MAX_K (ops.rs:18)
 
 // One 64-bit key per candidate: [63:32] the value's bits mapped to an order-preserving unsigned (with -0.0 == +0.0, as the reference's `>` sees them),
 // [31:1] ~index (so the LOWER index wins a tie; indices < 2^31), [0] "the value was -0.0" (to give back the original bits).  0 = not a candidate.
+__device__ __forceinline__ unsigned order_key(float v) {  // a > b <=> order_key(a) > order_key(b), with -0.0 == +0.0; NaN never gets here
+  const unsigned u = __float_as_uint(v + 0.0f);   // -0.0 -> +0.0
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float order_key_value(unsigned o) { return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o); }
 __device__ __forceinline__ unsigned long long key_of(float v, unsigned idx) {
   // NaN and -inf are never candidates (sort.cu:1552: candidate == candidate && candidate > -INFINITY)
   if (!(v == v) || v == -INFINITY) return 0ull;
-  const unsigned u = __float_as_uint(v + 0.0f);  // -0.0 -> +0.0
-  const unsigned o = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  const unsigned o = order_key(v);
   const unsigned low = ((~idx) << 1) | (__float_as_uint(v) == 0x80000000u ? 1u : 0u);
   return ((unsigned long long)o << 32) | (unsigned long long)low;
 }
 __device__ __forceinline__ unsigned idx_of(unsigned long long key) { return (~((unsigned)key >> 1)) & 0x7fffffffu; }
 __device__ __forceinline__ float val_of(unsigned long long key) {  // the candidate's original bits
-  const unsigned o = (unsigned)(key >> 32);
-  const unsigned u = (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o;
-  return __uint_as_float(((unsigned)key & 1u) ? 0x80000000u : u);
+  return ((unsigned)key & 1u) ? -0.0f : order_key_value((unsigned)(key >> 32));
 }
 // max over the wave, every lane gets it: DPP inside rows of 16 (xor 1, xor 2, half-row mirror, row mirror), then the four row results through v_readlane -- no LDS crossbar
 template <int CTRL> __device__ __forceinline__ unsigned long long dpp_u64(unsigned long long k) {
@@ -82,12 +100,55 @@ __device__ __forceinline__ float block_sum_ref_order(float v, float *warp_sums /
   return v;  // valid in thread 0
 }
 
+// ---- stage 1 shared by the three families.  A chunk of up to NT * MAXV logits lives in REGISTERS in the reference's thread-strided assignment (local = tid + NT j;
+// -inf beyond `width`): the per-thread partial sums below depend on exactly this assignment.
+__device__ __forceinline__ void load_chunk(const float *chunk, int width, float (&v)[MAXV]) {
+#pragma unroll
+  for (int j = 0; j < MAXV; ++j) {
+    const int local = threadIdx.x + j * NT;
+    v[j] = local < width ? chunk[local] : -INFINITY;
+  }
+}
+// the chunk's share of the softmax normaliser (sort.cu:1580-1597): sum of expf(x * inv_t - block_max), NaN if the chunk holds one, 0 when `empty` (nothing in the
+// chunk is selectable: block_max is -inf).  Expression, NaN rule and association are the reference's: nothing here may be reordered.  Valid in thread 0; two barriers.
+__device__ __forceinline__ float chunk_softmax_share(const float (&v)[MAXV], int width, float inv_t, float block_max, bool empty) {
+  __shared__ float s_warp_sums[32];
+  float local_sum = 0.0f;
+#pragma unroll
+  for (int j = 0; j < MAXV; ++j) {
+    const int local = threadIdx.x + j * NT;
+    if (local < width) {
+      const float c = v[j];
+      if (c != c) local_sum = NAN;
+      else if (!empty) local_sum += expf(c * inv_t - block_max);
+    }
+  }
+  return block_sum_ref_order(local_sum, s_warp_sums);
+}
+// workgroup max of the threads' `m` with a carried NaN flag (fmaxf drops a NaN, so a thread that met one passes nan = true and keeps it out of m): every thread gets
+// the max of the rest and, in `any_nan`, the OR of the flags.  A max and an OR: the fold order is free.  One barrier; one call per kernel (the LDS slots are not recycled).
+template <int WAVES> __device__ __forceinline__ float block_max_nan(float m, bool nan, bool &any_nan) {
+  __shared__ float s_wmax[WAVES];
+  __shared__ int s_wnan[WAVES];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  m = wave_max(m);
+  const bool wave_nan = __ballot(nan) != 0ull;
+  if (lane == 0) { s_wmax[wave] = m; s_wnan[wave] = wave_nan ? 1 : 0; }
+  __syncthreads();
+  int nans = 0;
+  float r = -INFINITY;
+#pragma unroll
+  for (int i = 0; i < WAVES; ++i) { nans |= s_wnan[i]; r = fmaxf(r, s_wmax[i]); }
+  any_nan = nans != 0;
+  return r;
+}
+
 struct Stage1Args {
   const float *input;
   float *block_values;
   uint32_t *block_indices;
   float *block_maxes, *block_sums;
-  const float *inv_temperatures;  // batched: one per row
+  const float *inv_temperatures;  // one per row, or NULL: every row takes the scalar
   float inv_temperature;
   int ncols, k, chunk_size, nblocks;
 };
@@ -124,29 +185,23 @@ __device__ __forceinline__ void head_merge(int nl, int k, int *heads /* LDS [nl]
   }
 }
 
-template <bool BATCHED>
 __global__ void __launch_bounds__(NT) topk_stage1_kernel(Stage1Args a) {
   __shared__ unsigned long long s_keys[4][MAX_K];  // each wave's sorted candidates
   __shared__ int s_heads[4];
-  __shared__ float s_warp_sums[32];
   __shared__ float s_block_max;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const size_t row = BATCHED ? blockIdx.y : 0;
+  const size_t row = blockIdx.y;
   const int chunk = blockIdx.x, k = a.k;
   const float *input = a.input + row * (size_t)a.ncols;
   float *bv = a.block_values + (row * a.nblocks + chunk) * (size_t)k;
   uint32_t *bi = a.block_indices + (row * a.nblocks + chunk) * (size_t)k;
-  const float inv_t = BATCHED ? a.inv_temperatures[row] : a.inv_temperature;
+  const float inv_t = a.inv_temperatures ? a.inv_temperatures[row] : a.inv_temperature;
   const int start = chunk * a.chunk_size, end = min(start + a.chunk_size, a.ncols), width = max(0, end - start);
-  // the chunk in registers, in the reference's thread-strided assignment (local = tid + 256 j): needed as it is for the partial sums below
   float v[MAXV];
   unsigned long long keys[MAXV];
+  load_chunk(input + start, width, v);
 #pragma unroll
-  for (int j = 0; j < MAXV; ++j) {
-    const int local = tid + j * NT;
-    v[j] = local < width ? input[start + local] : -INFINITY;
-    keys[j] = local < width ? key_of(v[j], (unsigned)(start + local)) : 0ull;
-  }
+  for (int j = 0; j < MAXV; ++j) keys[j] = key_of(v[j], (unsigned)(start + tid + j * NT));  // the -inf beyond the chunk is no candidate
   // ---- every wave: the k best of its 64 x MAXV logits, sorted.  Each lane first sorts ITS keys (descending, a bitonic network in registers), so that its
   // best unused key is always keys[0]; the round's winner shifts its array down by one.  A round = one wave-wide 64-bit max + 2 * MAXV moves in one lane.
 #pragma unroll
@@ -187,19 +242,8 @@ __global__ void __launch_bounds__(NT) topk_stage1_kernel(Stage1Args a) {
                });
   }
   __syncthreads();
-  // ---- the chunk's share of the softmax normaliser (sort.cu:1580-1597)
   const float block_max = s_block_max;
-  float local_sum = 0.0f;
-#pragma unroll
-  for (int j = 0; j < MAXV; ++j) {
-    const int local = tid + j * NT;
-    if (local < width) {
-      const float c = v[j];
-      if (c != c) local_sum = NAN;
-      else if (block_max != -INFINITY) local_sum += expf(c * inv_t - block_max);
-    }
-  }
-  const float block_sum = block_sum_ref_order(local_sum, s_warp_sums);
+  const float block_sum = chunk_softmax_share(v, width, inv_t, block_max, block_max == -INFINITY);
   if (tid == 0) {
     a.block_maxes[row * a.nblocks + chunk] = block_max;
     a.block_sums[row * a.nblocks + chunk] = block_sum;
@@ -217,14 +261,13 @@ struct Stage2Args {
   int nblocks, k, depth;
 };
 
-template <bool BATCHED>
 __global__ void __launch_bounds__(NT) topk_stage2_kernel(Stage2Args a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   int *heads = (int *)smem;  // [nblocks]
   __shared__ float s_warp_max[32], s_warp_sums[32];
   __shared__ float s_global_max;
   const int tid = threadIdx.x, lane = tid & 63, k = a.k, nb = a.nblocks;
-  const size_t row = BATCHED ? blockIdx.x : 0;
+  const size_t row = blockIdx.x;
   const float *bv = a.block_values + row * (size_t)nb * k;
   const uint32_t *bi = a.block_indices + row * (size_t)nb * k;
   const float *bm = a.block_maxes + row * (size_t)nb, *bs = a.block_sums + row * (size_t)nb;
@@ -275,7 +318,7 @@ static bool shape_ok(int ncols, int k, int chunk_size, int nblocks) {
 }
 static void run(const float *input, const float *inv_temperatures, float inv_temperature, float *block_values, uint32_t *block_indices, float *block_maxes,
                 float *block_sums, float *packed_out, float *values_out, uint32_t *indices_out, float *softmax_info_out, int nrows, int ncols, int k,
-                int chunk_size, int nblocks, bool batched, int64_t stream) {
+                int chunk_size, int nblocks, int64_t stream) {
   if (!shape_ok(ncols, k, chunk_size, nblocks) || nrows < 1) return;  // the reference's host wrapper validates before it calls (ops.rs:699-731)
   hipStream_t s = (hipStream_t)stream;
   Stage1Args a1{input, block_values, block_indices, block_maxes, block_sums, inv_temperatures, inv_temperature, ncols, k, chunk_size, nblocks};
@@ -284,13 +327,8 @@ static void run(const float *input, const float *inv_temperatures, float inv_tem
   const int depth = (int)std::min<size_t>((size_t)k, (60 * 1024 - heads_bytes) / 8 / (size_t)nblocks);  // keys staged per list (60 KiB of LDS in all; 0 = read from memory)
   Stage2Args a2{block_values, block_indices, block_maxes, block_sums, packed_out, values_out, indices_out, softmax_info_out, nblocks, k, depth};
   const size_t lds2 = heads_bytes + (size_t)nblocks * depth * 8;
-  if (batched) {
-    hipLaunchKernelGGL(topk_stage1_kernel<true>, dim3(nblocks, nrows), dim3(NT), 0, s, a1);
-    hipLaunchKernelGGL(topk_stage2_kernel<true>, dim3(nrows), dim3(NT), lds2, s, a2);
-  } else {
-    hipLaunchKernelGGL(topk_stage1_kernel<false>, dim3(nblocks), dim3(NT), 0, s, a1);
-    hipLaunchKernelGGL(topk_stage2_kernel<false>, dim3(1), dim3(NT), lds2, s, a2);
-  }
+  hipLaunchKernelGGL(topk_stage1_kernel, dim3(nblocks, nrows), dim3(NT), 0, s, a1);  // the row is the block index: a single row is a grid of 1 in that dimension
+  hipLaunchKernelGGL(topk_stage2_kernel, dim3(nrows), dim3(NT), lds2, s, a2);
 }
 
 // ---------------------------------------------------------------- greedy: top1_large_f32_packed[_batched] (sort.cu:1825-1912, 2071-2143, 2207-2238)
@@ -325,10 +363,9 @@ __device__ __forceinline__ void block_argmax(unsigned long long best, float val,
   }
   __syncthreads();
 }
-template <bool BATCHED>
 __global__ void __launch_bounds__(NT) top1_stage1_kernel(Top1Args a) {
   const int tid = threadIdx.x, chunk = blockIdx.x;
-  const size_t row = BATCHED ? blockIdx.y : 0;
+  const size_t row = blockIdx.y;
   const float *input = a.input + row * (size_t)a.ncols;
   const int start = chunk * a.chunk_size, end = min(start + a.chunk_size, a.ncols);
   unsigned long long best = 0ull;
@@ -347,10 +384,9 @@ __global__ void __launch_bounds__(NT) top1_stage1_kernel(Top1Args a) {
     a.block_indices[row * a.nblocks + chunk] = n || k == 0ull ? 0u : idx_of(k);
   }
 }
-template <bool BATCHED>
 __global__ void __launch_bounds__(NT) top1_stage2_kernel(Top1Args a) {
   const int tid = threadIdx.x;
-  const size_t row = BATCHED ? blockIdx.x : 0;
+  const size_t row = blockIdx.x;
   const float *bv = a.block_values + row * (size_t)a.nblocks;
   const uint32_t *bi = a.block_indices + row * (size_t)a.nblocks;
   unsigned long long best = 0ull;
@@ -371,25 +407,20 @@ __global__ void __launch_bounds__(NT) top1_stage2_kernel(Top1Args a) {
   }
 }
 static void run_top1(const float *input, float *block_values, uint32_t *block_indices, float *packed_out, uint32_t *token_ids_out, int nrows, int ncols, int chunk_size,
-                     int nblocks, bool batched, int64_t stream) {
+                     int nblocks, int64_t stream) {
   if (ncols <= 0 || chunk_size <= 0 || nblocks <= 0 || nrows <= 0 || (long long)nblocks * chunk_size < ncols) return;
   hipStream_t s = (hipStream_t)stream;
   Top1Args a{input, block_values, block_indices, packed_out, token_ids_out, ncols, chunk_size, nblocks};
-  if (batched) {
-    hipLaunchKernelGGL(top1_stage1_kernel<true>, dim3(nblocks, nrows), dim3(NT), 0, s, a);
-    hipLaunchKernelGGL(top1_stage2_kernel<true>, dim3(nrows), dim3(NT), 0, s, a);
-  } else {
-    hipLaunchKernelGGL(top1_stage1_kernel<false>, dim3(nblocks), dim3(NT), 0, s, a);
-    hipLaunchKernelGGL(top1_stage2_kernel<false>, dim3(1), dim3(NT), 0, s, a);
-  }
+  hipLaunchKernelGGL(top1_stage1_kernel, dim3(nblocks, nrows), dim3(NT), 0, s, a);
+  hipLaunchKernelGGL(top1_stage2_kernel, dim3(nrows), dim3(NT), 0, s, a);
 }
 
 // ---------------------------------------------------------------- temperature sampling over the whole row: categorical_large_f32_packed_batched
 // (the reference's symbol: ffi.rs:666, sort.cu:1825-2069, 2240-2257; callers ops.rs:1347-1500, sampler.rs:649-652, 744-764).  One draw per row from softmax(x * invT) by
 // inverting the cumulative distribution at the caller's uniform -- no top-k cut, nothing leaves the device but (token, logprob).
 // stage 1, one workgroup per chunk: block_values = the chunk's largest raw logit (NaN if it holds one, -inf if nothing is above -inf), block_sums = the chunk's
-//   sum of expf(x * invT - block_value * invT) -- the chunk is read ONCE into registers, max and sum both come from them; the sum keeps topk stage 1's association.
-// stage 2, one workgroup per row: gmax = max_b block_values * invT; the chunk masses block_sums[b] * expf(block_values[b] * invT - gmax) computed once by all
+//   sum of expf(x * invT - block_value * invT) -- the chunk is read ONCE into registers, max and sum both come from them; the sum IS top-k stage 1's (chunk_softmax_share).
+// stage 2, one workgroup per row, opens with row_preamble: gmax = max_b block_values * invT; the chunk masses block_sums[b] * expf(block_values[b] * invT - gmax) computed once by all
 //   threads, added in chunk order by thread 0 (running sums kept: the chunk that holds the target is a binary search over them); then the selected chunk, each thread
 //   owning a CONTIGUOUS run of ceil(chunk_size / 256) tokens: thread-local running sums, an inclusive scan of the thread totals across the lanes (DPP row rotates +
 //   v_readlane), the four wave totals through LDS with one barrier, and every thread tests its own tokens only.  Any chunk_size in 1..4096.
@@ -403,44 +434,24 @@ constexpr int CAT_MAXB = 4096;  // running chunk masses kept in LDS; the chunks 
 __device__ __forceinline__ bool finite_f32(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
 
 __global__ void __launch_bounds__(NT) cat_stage1_kernel(CatArgs a) {
-  __shared__ float s_warp_sums[32];
-  __shared__ float s_wmax[4];
-  __shared__ int s_wnan[4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, chunk = blockIdx.x;
+  const int tid = threadIdx.x, chunk = blockIdx.x;
   const size_t row = blockIdx.y;
   const float *input = a.input + row * (size_t)a.ncols;
   const float inv_t = a.inv_temperatures[row];
   const long long start = (long long)chunk * a.chunk_size, left = (long long)a.ncols - start;
   const int width = left <= 0 ? 0 : (left < a.chunk_size ? (int)left : a.chunk_size);
-  // the chunk in registers, thread-strided (local = tid + 256 j) as in topk stage 1: the partial sums below are the same partial sums
   float v[MAXV];
+  load_chunk(input + start, width, v);
   float m = -INFINITY;
-  bool nan = false;
+  bool nan = false, any_nan;
 #pragma unroll
   for (int j = 0; j < MAXV; ++j) {
-    const int local = tid + j * NT;
-    v[j] = local < width ? input[start + local] : -INFINITY;
     if (v[j] != v[j]) nan = true;
     else m = fmaxf(m, v[j]);
   }
-  m = wave_max(m);
-  const bool wave_nan = __ballot(nan) != 0ull;
-  if (lane == 0) { s_wmax[wave] = m; s_wnan[wave] = wave_nan ? 1 : 0; }
-  __syncthreads();
-  const bool any_nan = (s_wnan[0] | s_wnan[1] | s_wnan[2] | s_wnan[3]) != 0;
-  const float block_value = any_nan ? NAN : fmaxf(fmaxf(s_wmax[0], s_wmax[1]), fmaxf(s_wmax[2], s_wmax[3]));
-  const float block_max = block_value * inv_t;
-  float local_sum = 0.0f;
-#pragma unroll
-  for (int j = 0; j < MAXV; ++j) {
-    const int local = tid + j * NT;
-    if (local < width) {
-      const float c = v[j];
-      if (c != c) local_sum = NAN;
-      else if (block_value != -INFINITY) local_sum += expf(c * inv_t - block_max);
-    }
-  }
-  const float block_sum = block_sum_ref_order(local_sum, s_warp_sums);
+  m = block_max_nan<NT / 64>(m, nan, any_nan);
+  const float block_value = any_nan ? NAN : m;
+  const float block_sum = chunk_softmax_share(v, width, inv_t, block_value * inv_t, block_value == -INFINITY);
   if (tid == 0) {
     a.block_values[row * a.nblocks + chunk] = block_value;
     a.block_sums[row * a.nblocks + chunk] = block_sum;
@@ -469,10 +480,51 @@ __device__ __forceinline__ void wave_scan_f32(float v, float &excl, float &total
   total = o3 + r3;
 }
 
+// ---- the row preamble of both draws, for a workgroup of NTH threads over stage 1's workspace row (bv = chunk maxima, bs = chunk sums):
+//   gmax = max_b bv[b] * inv_t in every thread (NaN if a chunk reports one);
+//   the mass of chunk b under gmax is chunk_mass(b); all threads stage the first CAT_MAXB of them in s_cum, then THREAD 0 ALONE adds them in ascending chunk index
+//   (the chunks beyond CAT_MAXB recomputed on the way) and, with RUNNING_SUMS, leaves the running sums in s_cum (the categorical draw bisects them; the nucleus draw
+//   has no use for them, and the store after every load keeps the loop from running its LDS loads ahead: measured, profiles/sampling_refactor.md) -- the draws' denom
+//   is this sum and no other;
+//   `usable` = the row can be drawn from: inv_t and u in range, gmax and denom finite, denom > 0.
+// denom and usable are valid in thread 0 only, and no barrier follows thread 0's loop: the caller publishes what its other threads need.
+__device__ __forceinline__ float chunk_mass(const float *bv, const float *bs, int b, float inv_t, float gmax) { return bs[b] * expf(bv[b] * inv_t - gmax); }
+template <int NTH, bool RUNNING_SUMS>
+__device__ __forceinline__ float row_preamble(const float *bv, const float *bs, int nb, float inv_t, float u, float *s_cum /* LDS [CAT_MAXB] */, float &denom, bool &usable) {
+  const int tid = threadIdx.x;
+  float m = -INFINITY;
+  bool nan = false, any_nan;
+  for (int b = tid; b < nb; b += NTH) {
+    const float c = bv[b];
+    if (c != c) nan = true;
+    else m = fmaxf(m, c);
+  }
+  m = block_max_nan<NTH / 64>(m, nan, any_nan);
+  const float gmax = any_nan ? NAN : m * inv_t;
+  for (int b = tid; b < nb && b < CAT_MAXB; b += NTH) s_cum[b] = chunk_mass(bv, bs, b, inv_t, gmax);
+  __syncthreads();
+  denom = 0.0f;
+  usable = false;
+  if (tid == 0) {
+    float cum = 0.0f;
+    for (int b = 0; b < nb; ++b) {
+      cum += b < CAT_MAXB ? s_cum[b] : chunk_mass(bv, bs, b, inv_t, gmax);
+      if (RUNNING_SUMS && b < CAT_MAXB) s_cum[b] = cum;
+    }
+    denom = cum;
+    usable = inv_t > 0.0f && finite_f32(inv_t) && u >= 0.0f && u < 1.0f && finite_f32(gmax) && denom > 0.0f && finite_f32(denom);
+  }
+  return gmax;
+}
+// an unusable row: n NaNs (categorical_token / nucleus_token on the host refuse them)
+__device__ __forceinline__ void store_nan_row(float *packed, int n) {
+  for (int i = 0; i < n; ++i) packed[i] = NAN;
+}
+
 __global__ void __launch_bounds__(NT) cat_stage2_kernel(CatArgs a) {
   __shared__ float s_cum[CAT_MAXB];  // chunk masses, then their running sums
-  __shared__ float s_wmax[4], s_wtot[4], s_wlast[4];
-  __shared__ int s_wnan[4], s_wfirst[4];
+  __shared__ float s_wtot[4], s_wlast[4];
+  __shared__ int s_wfirst[4];
   __shared__ float s_denom, s_target;
   __shared__ int s_sel;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nb = a.nblocks;
@@ -480,36 +532,15 @@ __global__ void __launch_bounds__(NT) cat_stage2_kernel(CatArgs a) {
   const float *input = a.input + row * (size_t)a.ncols;
   const float *bv = a.block_values + row * (size_t)nb, *bs = a.block_sums + row * (size_t)nb;
   float *packed = a.packed_out + row * 2;
-  const float inv_t = a.inv_temperatures[row];
-  // ---- gmax (fmaxf drops a NaN: it is carried as a flag)
-  float m = -INFINITY;
-  bool nan = false;
-  for (int b = tid; b < nb; b += NT) {
-    const float c = bv[b];
-    if (c != c) nan = true;
-    else m = fmaxf(m, c);
-  }
-  m = wave_max(m);
-  const bool wave_nan = __ballot(nan) != 0ull;
-  if (lane == 0) { s_wmax[wave] = m; s_wnan[wave] = wave_nan ? 1 : 0; }
-  __syncthreads();
-  const bool any_nan = (s_wnan[0] | s_wnan[1] | s_wnan[2] | s_wnan[3]) != 0;
-  const float gmax = any_nan ? NAN : fmaxf(fmaxf(s_wmax[0], s_wmax[1]), fmaxf(s_wmax[2], s_wmax[3])) * inv_t;
-  // ---- the chunk masses, once
-  auto mass = [&](int b) { return bs[b] * expf(bv[b] * inv_t - gmax); };
-  for (int b = tid; b < nb && b < CAT_MAXB; b += NT) s_cum[b] = mass(b);
-  __syncthreads();
-  // ---- thread 0: denom in chunk order, the target, the chunk that holds it
+  const float inv_t = a.inv_temperatures[row], u = a.uniforms[row];
+  float denom;
+  bool usable;
+  const float gmax = row_preamble<NT, true>(bv, bs, nb, inv_t, u, s_cum, denom, usable);
+  // ---- thread 0: the target, the chunk that holds it
   if (tid == 0) {
-    float cum = 0.0f;
-    for (int b = 0; b < nb; ++b) {
-      cum += b < CAT_MAXB ? s_cum[b] : mass(b);
-      if (b < CAT_MAXB) s_cum[b] = cum;
-    }
-    const float denom = cum, u = a.uniforms[row];
     int sel = -1;
     float target = NAN;
-    if (inv_t > 0.0f && finite_f32(inv_t) && u >= 0.0f && u < 1.0f && finite_f32(gmax) && denom > 0.0f && finite_f32(denom)) {
+    if (usable) {
       target = fminf(u * denom, nextafterf(denom, -INFINITY));
       const int nl = nb < CAT_MAXB ? nb : CAT_MAXB;
       float before = 0.0f;
@@ -525,7 +556,7 @@ __global__ void __launch_bounds__(NT) cat_stage2_kernel(CatArgs a) {
       } else {  // beyond the staged chunks: walk on
         float c = s_cum[nl - 1];
         for (int b = nl; b < nb; ++b) {
-          const float next = c + mass(b);
+          const float next = c + chunk_mass(bv, bs, b, inv_t, gmax);
           if (target < next) { sel = b; before = c; break; }
           c = next;
         }
@@ -535,7 +566,7 @@ __global__ void __launch_bounds__(NT) cat_stage2_kernel(CatArgs a) {
     s_sel = sel;
     s_target = target;
     s_denom = denom;
-    if (sel < 0) { packed[0] = NAN; packed[1] = NAN; }
+    if (sel < 0) store_nan_row(packed, 2);
   }
   __syncthreads();
   const int sel = s_sel;
@@ -579,15 +610,18 @@ __global__ void __launch_bounds__(NT) cat_stage2_kernel(CatArgs a) {
     int token = -1;
     for (int i = 3; i >= 0; --i) if (s_wfirst[i] >= 0) token = s_wfirst[i];
     if (token < 0) token = (int)fmaxf(fmaxf(s_wlast[0], s_wlast[1]), fmaxf(s_wlast[2], s_wlast[3]));
-    if (token < 0) { packed[0] = NAN; packed[1] = NAN; return; }  // unreachable while the chunk's mass is > 0
+    if (token < 0) { store_nan_row(packed, 2); return; }  // unreachable while the chunk's mass is > 0
     packed[0] = (float)(start + token);
     packed[1] = input[start + token] * inv_t - gmax - logf(s_denom);
   }
 }
 
+static bool draw_shape_ok(int nrows, int ncols, int chunk_size, int nblocks) {  // the refusals of both draws: their stage 1 is the same launch
+  return nrows >= 1 && ncols >= 1 && chunk_size >= 1 && chunk_size <= NT * MAXV && (long long)nblocks * chunk_size >= ncols;
+}
 static void run_categorical(const float *input, const float *inv_temperatures, const float *uniforms, float *block_values, float *block_sums, float *packed_out, int nrows,
                             int ncols, int chunk_size, int nblocks, int64_t stream) {
-  if (nrows < 1 || ncols < 1 || chunk_size < 1 || chunk_size > NT * MAXV || (long long)nblocks * chunk_size < ncols) return;
+  if (!draw_shape_ok(nrows, ncols, chunk_size, nblocks)) return;
   hipStream_t s = (hipStream_t)stream;
   CatArgs a{input, inv_temperatures, uniforms, block_values, block_sums, packed_out, ncols, chunk_size, nblocks};
   hipLaunchKernelGGL(cat_stage1_kernel, dim3(nblocks, nrows), dim3(NT), 0, s, a);
@@ -597,7 +631,7 @@ static void run_categorical(const float *input, const float *inv_temperatures, c
 // ---------------------------------------------------------------- top-p / min-p over the whole row: mrs_nucleus_large_f32_packed_batched (no reference counterpart:
 // with top-k unset and a cut active the reference leaves the device, sampler.rs:649-655, and sorts the whole vocabulary on the host, sampler.rs:1605-1662).
 // stage 1 is cat_stage1_kernel as it is, so denom is the categorical denom.  stage 2, one workgroup of 1024 threads per row:
-//   gmax, denom (chunk order, thread 0) and the row's validity as in cat_stage2_kernel;
+//   gmax, denom (chunk order, thread 0) and the row's validity from row_preamble, on 16 waves;
 //   every mass after that is a FIXED-POINT INTEGER, q_i = (u64)(expf(x_i * invT - gmax) * 2^39): integer adds are exact in any order, so the histogram below may use
 //   LDS atomics, and x*, the kept mass and the drawn token are functions of the row's f32 weights alone -- bit-identical whatever the launch, the batch row or the
 //   neighbours are.  (2^39, not 2^40: 2^24 tokens of weight 1 sum to 2^63 and cannot wrap; the largest weight is exactly 1 under -ffp-contract=off and 1 to within rounding otherwise.  The truncation costs at most ncols * 2^-39 of absolute mass.)
@@ -617,11 +651,6 @@ struct NucArgs {
 constexpr int NUC_NT = 1024, NUC_WAVES = NUC_NT / 64, NUC_UNROLL = 8;
 typedef unsigned long long u64;
 
-__device__ __forceinline__ unsigned order_key(float v) {  // a > b <=> order_key(a) > order_key(b), with -0.0 == +0.0; NaN never gets here
-  const unsigned u = __float_as_uint(v + 0.0f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float order_key_value(unsigned o) { return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o); }
 __device__ __forceinline__ u64 fixed_mass(float w) { return (u64)(w * 549755813888.0f); }  // 2^39: the product is exact, the conversion truncates
 __device__ __forceinline__ u64 wave_sum_u64(u64 v) {
 #pragma unroll
@@ -640,9 +669,7 @@ __device__ __forceinline__ u64 wave_scan_u64(u64 v) {  // inclusive
 
 __global__ void __launch_bounds__(NUC_NT) nuc_stage2_kernel(NucArgs a) {
   __shared__ u64 s_hist[NUC_WAVES][256];
-  __shared__ float s_cum[CAT_MAXB];
-  __shared__ float s_wmax[NUC_WAVES];
-  __shared__ int s_wnan[NUC_WAVES];
+  __shared__ float s_cum[CAT_MAXB];  // the preamble's staging of the chunk masses
   __shared__ u64 s_wkept[NUC_WAVES], s_wall[NUC_WAVES], s_wscan[NUC_WAVES];
   __shared__ float s_denom;
   __shared__ int s_ok, s_digit;
@@ -651,35 +678,15 @@ __global__ void __launch_bounds__(NUC_NT) nuc_stage2_kernel(NucArgs a) {
   const float *input = a.input + row * (size_t)n;
   const float *bv = a.block_values + row * (size_t)nb, *bs = a.block_sums + row * (size_t)nb;
   float *packed = a.packed_out + row * 4;
-  const float inv_t = a.inv_temperatures[row], top_p = a.top_ps[row], min_p = a.min_ps[row];
+  const float inv_t = a.inv_temperatures[row], u = a.uniforms[row], top_p = a.top_ps[row], min_p = a.min_ps[row];
   const bool cut_p = top_p > 0.0f && top_p < 1.0f, cut_m = min_p > 0.0f && min_p < 1.0f;  // NaN: no cut
-  // ---- gmax, denom, validity: cat_stage2_kernel's, on 16 waves
-  float m = -INFINITY;
-  bool nan = false;
-  for (int b = tid; b < nb; b += NUC_NT) {
-    const float c = bv[b];
-    if (c != c) nan = true;
-    else m = fmaxf(m, c);
-  }
-  m = wave_max(m);
-  const bool wave_nan = __ballot(nan) != 0ull;
-  if (lane == 0) { s_wmax[wave] = m; s_wnan[wave] = wave_nan ? 1 : 0; }
-  __syncthreads();
-  bool any_nan = false;
-  float rmax = -INFINITY;
-  for (int i = 0; i < NUC_WAVES; ++i) { any_nan = any_nan || s_wnan[i] != 0; rmax = fmaxf(rmax, s_wmax[i]); }
-  const float gmax = any_nan ? NAN : rmax * inv_t;
-  auto mass = [&](int b) { return bs[b] * expf(bv[b] * inv_t - gmax); };
-  for (int b = tid; b < nb && b < CAT_MAXB; b += NUC_NT) s_cum[b] = mass(b);
-  __syncthreads();
+  float denom;
+  bool usable;
+  const float gmax = row_preamble<NUC_NT, false>(bv, bs, nb, inv_t, u, s_cum, denom, usable);
   if (tid == 0) {
-    float cum = 0.0f;
-    for (int b = 0; b < nb; ++b) cum += b < CAT_MAXB ? s_cum[b] : mass(b);
-    const float u = a.uniforms[row];
-    const bool ok = inv_t > 0.0f && finite_f32(inv_t) && u >= 0.0f && u < 1.0f && finite_f32(gmax) && cum > 0.0f && finite_f32(cum);
-    s_denom = cum;
-    s_ok = ok ? 1 : 0;
-    if (!ok) { packed[0] = NAN; packed[1] = NAN; packed[2] = NAN; packed[3] = NAN; }
+    s_denom = denom;
+    s_ok = usable ? 1 : 0;
+    if (!usable) store_nan_row(packed, 4);
   }
   __syncthreads();
   if (!s_ok) return;
@@ -739,7 +746,7 @@ __global__ void __launch_bounds__(NUC_NT) nuc_stage2_kernel(NucArgs a) {
       __syncthreads();
       const int digit = s_digit;
       if (digit < 0) {  // unreachable: the cumulative mass ends at the bin mass the previous pass selected, which had reached the cutoff
-        if (tid == 0) { packed[0] = NAN; packed[1] = NAN; packed[2] = NAN; packed[3] = NAN; }
+        if (tid == 0) store_nan_row(packed, 4);
         return;
       }
       kstar |= (unsigned)digit << shift;
@@ -779,10 +786,10 @@ __global__ void __launch_bounds__(NUC_NT) nuc_stage2_kernel(NucArgs a) {
   u64 kept = 0ull, all = 0ull, before = 0ull;
   for (int w = 0; w < NUC_WAVES; ++w) { kept += s_wkept[w]; all += s_wall[w]; }
   if (kept == 0ull) {  // unreachable: the arg-max has weight 1 (to within rounding in a contracted build) and passes both cuts
-    if (tid == 0) { packed[0] = NAN; packed[1] = NAN; packed[2] = NAN; packed[3] = NAN; }
+    if (tid == 0) store_nan_row(packed, 4);
     return;
   }
-  u64 target = (u64)((double)a.uniforms[row] * (double)kept);
+  u64 target = (u64)((double)u * (double)kept);
   if (target >= kept) target = kept - 1ull;
   int sel = NUC_WAVES - 1;
   for (int w = 0; w < NUC_WAVES; ++w) {
@@ -818,7 +825,7 @@ __global__ void __launch_bounds__(NUC_NT) nuc_stage2_kernel(NucArgs a) {
 
 static void run_nucleus(const float *input, const float *inv_temperatures, const float *uniforms, const float *top_ps, const float *min_ps, float *block_values,
                         float *block_sums, float *packed_out, int nrows, int ncols, int chunk_size, int nblocks, int64_t stream) {
-  if (nrows < 1 || ncols < 1 || chunk_size < 1 || chunk_size > NT * MAXV || (long long)nblocks * chunk_size < ncols) return;  // run_categorical's refusals
+  if (!draw_shape_ok(nrows, ncols, chunk_size, nblocks)) return;
   hipStream_t s = (hipStream_t)stream;
   CatArgs a1{input, inv_temperatures, uniforms, block_values, block_sums, nullptr, ncols, chunk_size, nblocks};
   NucArgs a2{input, inv_temperatures, uniforms, top_ps, min_ps, block_values, block_sums, packed_out, ncols, chunk_size, nblocks};
@@ -863,25 +870,25 @@ extern "C" void topk_large_f32(const float *input, float *block_values, uint32_t
                                uint32_t *indices_out, float *softmax_info_out, int ncols, int k, int chunk_size, int nblocks, float inv_temperature,
                                int64_t stream) {
   mrs::sampling::run(input, nullptr, inv_temperature, block_values, block_indices, block_maxes, block_sums, nullptr, values_out, indices_out, softmax_info_out, 1,
-                     ncols, k, chunk_size, nblocks, false, stream);
+                     ncols, k, chunk_size, nblocks, stream);
 }
 extern "C" void topk_large_f32_packed(const float *input, float *block_values, uint32_t *block_indices, float *block_maxes, float *block_sums, float *packed_out,
                                       int ncols, int k, int chunk_size, int nblocks, float inv_temperature, int64_t stream) {
   mrs::sampling::run(input, nullptr, inv_temperature, block_values, block_indices, block_maxes, block_sums, packed_out, nullptr, nullptr, nullptr, 1, ncols, k,
-                     chunk_size, nblocks, false, stream);
+                     chunk_size, nblocks, stream);
 }
 extern "C" void topk_large_f32_packed_batched(const float *input, const float *inv_temperatures, float *block_values, uint32_t *block_indices, float *block_maxes,
                                               float *block_sums, float *packed_out, int nrows, int ncols, int k, int chunk_size, int nblocks, int64_t stream) {
   mrs::sampling::run(input, inv_temperatures, 0.0f, block_values, block_indices, block_maxes, block_sums, packed_out, nullptr, nullptr, nullptr, nrows, ncols, k,
-                     chunk_size, nblocks, true, stream);
+                     chunk_size, nblocks, stream);
 }
 extern "C" void top1_large_f32_packed(const float *input, float *block_values, uint32_t *block_indices, float *packed_out, uint32_t *token_ids_out, int ncols,
                                       int chunk_size, int nblocks, int64_t stream) {
-  mrs::sampling::run_top1(input, block_values, block_indices, packed_out, token_ids_out, 1, ncols, chunk_size, nblocks, false, stream);
+  mrs::sampling::run_top1(input, block_values, block_indices, packed_out, token_ids_out, 1, ncols, chunk_size, nblocks, stream);
 }
 extern "C" void top1_large_f32_packed_batched(const float *input, float *block_values, uint32_t *block_indices, float *packed_out, uint32_t *token_ids_out, int nrows,
                                               int ncols, int chunk_size, int nblocks, int64_t stream) {
-  mrs::sampling::run_top1(input, block_values, block_indices, packed_out, token_ids_out, nrows, ncols, chunk_size, nblocks, true, stream);
+  mrs::sampling::run_top1(input, block_values, block_indices, packed_out, token_ids_out, nrows, ncols, chunk_size, nblocks, stream);
 }
 extern "C" void categorical_large_f32_packed_batched(const float *input, const float *inv_temperatures, const float *uniforms, float *block_values, float *block_sums,
                                                      float *packed_out, int nrows, int ncols, int chunk_size, int nblocks, int64_t stream) {

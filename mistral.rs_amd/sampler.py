@@ -23,26 +23,68 @@ MAX_K = 128            # CUDA_TOPK_MAX_K (ops.rs:18)
 MAX_STAGE2 = 47 * 1024  # CUDA_TOPK_MAX_STAGE2_CANDIDATES (ops.rs:20)
 
 
-class TopK:
+class _Workspace:
+    """What the four launchers below share: the shape checks and `nblocks`, the logits rows, and the per-row parameters.  `NAME` prefixes a class's refusals
+    ("top-k: ..."); `NOUN` opens the ones about its parameters ("top-k requires ...").  The draws return token ids as f32 and put the rows into a grid dimension:
+    `draw_limits` refuses what does not fit there (top-k and top-1 have no such limits)."""
+    NAME = NOUN = ""
+
+    def __init__(self, vocab, device, max_rows, draw_limits=False):
+        if vocab <= 0:
+            raise ValueError(f"{self.NAME}: empty logits")
+        if draw_limits and vocab > 2 ** 24:
+            raise ValueError(f"{self.NAME}: vocab={vocab} exceeds 2**24 (token ids come back as f32)")  # ops.rs:1387
+        if draw_limits and (max_rows < 1 or max_rows > 65535):
+            raise ValueError(f"{self.NAME}: max_rows={max_rows} must be in [1, 65535]")
+        self.vocab, self.max_rows, self.device = vocab, max_rows, device
+        self.nblocks = (vocab + CHUNK_SIZE - 1) // CHUNK_SIZE
+
+    def _f32(self, *shape):
+        return torch.empty(*shape, dtype=torch.float32, device=self.device)
+
+    def _rows(self, logits):
+        """the logits as [rows, vocab]: contiguous f32, at most max_rows rows"""
+        x = logits.reshape(-1, self.vocab) if logits.dim() > 1 else logits.reshape(1, self.vocab)
+        if x.dtype != torch.float32 or not x.is_contiguous() or x.shape[0] > self.max_rows:
+            raise ValueError(f"{self.NAME}: logits must be contiguous f32 with at most max_rows rows")
+        return x, x.shape[0]
+
+    def _inv_temperatures(self, temperature, rows):
+        """one positive finite temperature per row (or one for all) -> the f32 inverse temperatures"""
+        temps = np.broadcast_to(np.asarray(temperature, dtype=np.float64), (rows,))
+        if not np.all(np.isfinite(temps) & (temps > 0)):
+            raise ValueError(f"{self.NOUN} requires a positive finite temperature")
+        return (1.0 / temps).astype(np.float32)
+
+    def _uniforms(self, uniforms, rows):
+        u = np.asarray(uniforms, dtype=np.float32).reshape(-1)
+        if u.shape[0] != rows or not np.all((u >= 0) & (u < 1)):
+            raise ValueError(f"{self.NOUN} requires one uniform in [0, 1) per row")
+        return u
+
+    def _upload(self, params, rows):
+        """the stacked per-row parameters in ONE copy into self._params [len(params), max_rows]; returns the device pointer of each"""
+        self._params[:, :rows].copy_(torch.from_numpy(np.stack(params)), non_blocking=False)
+        return [self._params[j].data_ptr() for j in range(len(params))]
+
+
+class TopK(_Workspace):
     """Workspace + launcher for rows of `vocab` f32 logits (cuda_topk_logits_f32_packed / _batched, ops.rs:691-1000)."""
+    NAME = NOUN = "top-k"
 
     def __init__(self, vocab: int, k: int, device, max_rows: int = 1):
         k = min(int(k), int(vocab))
-        if vocab <= 0:
-            raise ValueError("top-k: empty logits")
+        super().__init__(vocab, device, max_rows)
         if k == 0 or k > MAX_K:
             raise ValueError(f"top-k: k={k} must be in [1, {MAX_K}]")
-        self.vocab, self.k, self.max_rows, self.device = vocab, k, max_rows, device
-        self.nblocks = (vocab + CHUNK_SIZE - 1) // CHUNK_SIZE
+        self.k = k
         if self.nblocks * k > MAX_STAGE2:
             raise ValueError(f"top-k workspace too large: {self.nblocks * k} candidates")
-        f32 = dict(dtype=torch.float32, device=device)
-        self.block_values = torch.empty(max_rows, self.nblocks, k, **f32)
+        self.block_values = self._f32(max_rows, self.nblocks, k)
         self.block_indices = torch.empty(max_rows, self.nblocks, k, dtype=torch.int32, device=device)
-        self.block_maxes = torch.empty(max_rows, self.nblocks, **f32)
-        self.block_sums = torch.empty(max_rows, self.nblocks, **f32)
-        self.packed = torch.empty(max_rows, 2 * k + 2, **f32)
-        self._inv_t = torch.empty(max_rows, **f32)
+        self.block_maxes, self.block_sums = self._f32(max_rows, self.nblocks), self._f32(max_rows, self.nblocks)
+        self.packed = self._f32(max_rows, 2 * k + 2)
+        self._params = self._f32(1, max_rows)  # the inverse temperatures of a batched call
         vp, i, f, ll = C.c_void_p, C.c_int, C.c_float, C.c_int64
         self._one = _lib.sym("core", "topk_large_f32_packed", [vp, vp, vp, vp, vp, vp, i, i, i, i, f, ll])
         self._many = _lib.sym("core", "topk_large_f32_packed_batched", [vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, ll])
@@ -50,43 +92,32 @@ class TopK:
     def __call__(self, logits: torch.Tensor, temperature) -> torch.Tensor:
         """logits f32 [vocab] or [rows, vocab] (contiguous, on the device); temperature: a positive finite float, or one per row.  Returns the packed rows
         [rows, 2k + 2] on the device (a view of this object's buffer: consume it before the next call)."""
-        x = logits.reshape(-1, self.vocab) if logits.dim() > 1 else logits.reshape(1, self.vocab)
-        rows = x.shape[0]
-        if x.dtype != torch.float32 or not x.is_contiguous() or rows > self.max_rows:
-            raise ValueError("top-k: logits must be contiguous f32 with at most max_rows rows")
-        temps = np.broadcast_to(np.asarray(temperature, dtype=np.float64), (rows,))
-        if not np.all(np.isfinite(temps) & (temps > 0)):
-            raise ValueError("top-k requires a positive finite temperature")
+        x, rows = self._rows(logits)
+        inv_t = self._inv_temperatures(temperature, rows)
         st = torch.cuda.current_stream().cuda_stream
         if rows == 1:
             self._one(x.data_ptr(), self.block_values.data_ptr(), self.block_indices.data_ptr(), self.block_maxes.data_ptr(), self.block_sums.data_ptr(),
-                      self.packed.data_ptr(), self.vocab, self.k, CHUNK_SIZE, self.nblocks, float(np.float32(1.0 / temps[0])), st)
+                      self.packed.data_ptr(), self.vocab, self.k, CHUNK_SIZE, self.nblocks, float(inv_t[0]), st)
         else:
-            self._inv_t[:rows].copy_(torch.from_numpy((1.0 / temps).astype(np.float32)), non_blocking=False)
-            self._many(x.data_ptr(), self._inv_t.data_ptr(), self.block_values.data_ptr(), self.block_indices.data_ptr(), self.block_maxes.data_ptr(),
+            self._many(x.data_ptr(), self._upload([inv_t], rows)[0], self.block_values.data_ptr(), self.block_indices.data_ptr(), self.block_maxes.data_ptr(),
                        self.block_sums.data_ptr(), self.packed.data_ptr(), rows, self.vocab, self.k, CHUNK_SIZE, self.nblocks, st)
         return self.packed[:rows]
 
 
-class Top1:
+class Top1(_Workspace):
     """Greedy rows: `top1_large_f32_packed[_batched]` (cuda_top1_logits_f32_*, ops.rs:1232-2050) -- packed [rows][2] = (max logit, token id as f32); no temperature."""
+    NAME = "top-1"
 
     def __init__(self, vocab: int, device, max_rows: int = 1):
-        if vocab <= 0:
-            raise ValueError("top-1: empty logits")
-        self.vocab, self.max_rows, self.device = vocab, max_rows, device
-        self.nblocks = (vocab + CHUNK_SIZE - 1) // CHUNK_SIZE
-        self.block_values = torch.empty(max_rows, self.nblocks, dtype=torch.float32, device=device)
+        super().__init__(vocab, device, max_rows)
+        self.block_values = self._f32(max_rows, self.nblocks)
         self.block_indices = torch.empty(max_rows, self.nblocks, dtype=torch.int32, device=device)
-        self.packed = torch.empty(max_rows, 2, dtype=torch.float32, device=device)
+        self.packed = self._f32(max_rows, 2)
         vp, i, ll = C.c_void_p, C.c_int, C.c_int64
         self._many = _lib.sym("core", "top1_large_f32_packed_batched", [vp, vp, vp, vp, vp, i, i, i, i, ll])
 
     def __call__(self, logits: torch.Tensor) -> torch.Tensor:
-        x = logits.reshape(-1, self.vocab)
-        rows = x.shape[0]
-        if x.dtype != torch.float32 or not x.is_contiguous() or rows > self.max_rows:
-            raise ValueError("top-1: logits must be contiguous f32 with at most max_rows rows")
+        x, rows = self._rows(logits.reshape(-1, self.vocab))
         self._many(x.data_ptr(), self.block_values.data_ptr(), self.block_indices.data_ptr(), self.packed.data_ptr(), None, rows, self.vocab, CHUNK_SIZE, self.nblocks,
                    torch.cuda.current_stream().cuda_stream)
         return self.packed[:rows]
@@ -138,43 +169,24 @@ def sample(packed: np.ndarray, k: int, temperature: float, top_p: float, min_p: 
     return int(ids[j]), float(rep[j])
 
 
-class Categorical:
+class Categorical(_Workspace):
     """Workspace + launcher of the device categorical draw over rows of `vocab` f32 logits (cuda_categorical_logits_f32_packed_batched, ops.rs:1347-1500)."""
+    NAME = NOUN = "categorical"
 
     def __init__(self, vocab: int, device, max_rows: int = 1):
-        vocab, max_rows = int(vocab), int(max_rows)
-        if vocab <= 0:
-            raise ValueError("categorical: empty logits")
-        if vocab > 2 ** 24:
-            raise ValueError(f"categorical: vocab={vocab} exceeds 2**24 (token ids come back as f32)")  # ops.rs:1387
-        if max_rows < 1 or max_rows > 65535:
-            raise ValueError(f"categorical: max_rows={max_rows} must be in [1, 65535]")
-        self.vocab, self.max_rows, self.device = vocab, max_rows, device
-        self.nblocks = (vocab + CHUNK_SIZE - 1) // CHUNK_SIZE
-        f32 = dict(dtype=torch.float32, device=device)
-        self.block_values = torch.empty(max_rows, self.nblocks, **f32)
-        self.block_sums = torch.empty(max_rows, self.nblocks, **f32)
-        self.packed = torch.empty(max_rows, 2, **f32)
-        self._params = torch.empty(2, max_rows, **f32)  # [0] inverse temperatures, [1] uniforms: one upload
+        super().__init__(int(vocab), device, int(max_rows), draw_limits=True)
+        self.block_values, self.block_sums = self._f32(self.max_rows, self.nblocks), self._f32(self.max_rows, self.nblocks)
+        self.packed = self._f32(self.max_rows, 2)
+        self._params = self._f32(2, self.max_rows)  # [0] inverse temperatures, [1] uniforms: one upload
         vp, i, ll = C.c_void_p, C.c_int, C.c_int64
         self._many = _lib.sym("core", "categorical_large_f32_packed_batched", [vp, vp, vp, vp, vp, vp, i, i, i, i, ll])
 
     def __call__(self, logits: torch.Tensor, temperature, uniforms) -> torch.Tensor:
         """logits f32 [vocab] or [rows, vocab] (contiguous, on the device); temperature: a positive finite float, or one per row; uniforms: one value in [0, 1)
         per row.  Returns the packed rows [rows, 2] = (token id, logprob) on the device (a view of this object's buffer: consume it before the next call)."""
-        x = logits.reshape(-1, self.vocab) if logits.dim() > 1 else logits.reshape(1, self.vocab)
-        rows = x.shape[0]
-        if x.dtype != torch.float32 or not x.is_contiguous() or rows > self.max_rows:
-            raise ValueError("categorical: logits must be contiguous f32 with at most max_rows rows")
-        temps = np.broadcast_to(np.asarray(temperature, dtype=np.float64), (rows,))
-        if not np.all(np.isfinite(temps) & (temps > 0)):
-            raise ValueError("categorical requires a positive finite temperature")
-        u = np.asarray(uniforms, dtype=np.float32).reshape(-1)
-        if u.shape[0] != rows or not np.all((u >= 0) & (u < 1)):
-            raise ValueError("categorical requires one uniform in [0, 1) per row")
-        params = np.stack([(1.0 / temps).astype(np.float32), u])
-        self._params[:, :rows].copy_(torch.from_numpy(params), non_blocking=False)
-        self._many(x.data_ptr(), self._params[0].data_ptr(), self._params[1].data_ptr(), self.block_values.data_ptr(), self.block_sums.data_ptr(),
+        x, rows = self._rows(logits)
+        pr = self._upload([self._inv_temperatures(temperature, rows), self._uniforms(uniforms, rows)], rows)
+        self._many(x.data_ptr(), pr[0], pr[1], self.block_values.data_ptr(), self.block_sums.data_ptr(),
                    self.packed.data_ptr(), rows, self.vocab, CHUNK_SIZE, self.nblocks, torch.cuda.current_stream().cuda_stream)
         return self.packed[:rows]
 
@@ -193,19 +205,25 @@ def uniform_for(seed: int, index: int) -> np.float32:
     return np.float32(np.random.default_rng((int(seed), int(index))).random(dtype=np.float32))
 
 
-def categorical_host(logits_row, inv_temperature, uniform):
-    """The contract of `categorical_large_f32_packed_batched` for one row in numpy f32 (one chunk, additions in index order): (token, logprob).  Raises like
-    `categorical_token` where the device reports (NaN, NaN)."""
+def _host_weights(logits_row, inv_temperature, uniform):
+    """The opening of both host rules: (x, inv_t, u, gmax, w) with the f32 weights w = exp(x * inv_t - gmax) -- all of them in [0, 1] -- or w = None where inv_t, u or
+    gmax already make the row unusable.  The rules add the weights into `denom` each in its own way, ON PURPOSE."""
     x, inv_t, u = np.asarray(logits_row, dtype=np.float32).reshape(-1), np.float32(inv_temperature), np.float32(uniform)
     with np.errstate(over="ignore", invalid="ignore"):
         gmax = np.float32(x.max() * inv_t) if x.size else np.float32(np.nan)
         ok = np.isfinite(inv_t) and inv_t > 0 and np.isfinite(u) and 0 <= u < 1 and np.isfinite(gmax)
-        if ok:
-            w = np.exp((x * inv_t - gmax).astype(np.float32), dtype=np.float32)
-            cum = np.cumsum(w, dtype=np.float32)  # sequential f32 additions
-            denom = cum[-1]
-            ok = np.isfinite(denom) and denom > 0
-    if not ok:
+        w = np.exp((x * inv_t - gmax).astype(np.float32), dtype=np.float32) if ok else None
+    return x, inv_t, u, gmax, w
+
+
+def categorical_host(logits_row, inv_temperature, uniform):
+    """The contract of `categorical_large_f32_packed_batched` for one row in numpy f32 (one chunk, additions in index order): (token, logprob).  Raises like
+    `categorical_token` where the device reports (NaN, NaN)."""
+    x, inv_t, u, gmax, w = _host_weights(logits_row, inv_temperature, uniform)
+    if w is not None:
+        cum = np.cumsum(w, dtype=np.float32)  # SEQUENTIAL f32 additions: the running sums the draw inverts, denom their last (nucleus_host: a pairwise sum)
+        denom = cum[-1]
+    if w is None or not (np.isfinite(denom) and denom > 0):
         raise ValueError("invalid batched CUDA categorical output")
     target = min(np.float32(u * denom), np.nextafter(denom, np.float32(-np.inf)))
     hit = np.nonzero((w > 0) & (cum > target))[0]
@@ -213,25 +231,16 @@ def categorical_host(logits_row, inv_temperature, uniform):
     return tok, float(np.float32(np.float32(x[tok] * inv_t - gmax) - np.log(denom, dtype=np.float32)))
 
 
-class Nucleus:
+class Nucleus(_Workspace):
     """Workspace + launcher of the device top-p / min-p draw over rows of `vocab` f32 logits (`mrs_nucleus_large_f32_packed_batched`; the reference has no device path
     for this case, sampler.rs:649-655).  Per-row temperature, uniform, top_p and min_p; a cut outside (0, 1) is inactive."""
+    NAME = NOUN = "nucleus"
 
     def __init__(self, vocab: int, device, max_rows: int = 1):
-        vocab, max_rows = int(vocab), int(max_rows)
-        if vocab <= 0:
-            raise ValueError("nucleus: empty logits")
-        if vocab > 2 ** 24:
-            raise ValueError(f"nucleus: vocab={vocab} exceeds 2**24 (token ids come back as f32)")
-        if max_rows < 1 or max_rows > 65535:
-            raise ValueError(f"nucleus: max_rows={max_rows} must be in [1, 65535]")
-        self.vocab, self.max_rows, self.device = vocab, max_rows, device
-        self.nblocks = (vocab + CHUNK_SIZE - 1) // CHUNK_SIZE
-        f32 = dict(dtype=torch.float32, device=device)
-        self.block_values = torch.empty(max_rows, self.nblocks, **f32)
-        self.block_sums = torch.empty(max_rows, self.nblocks, **f32)
-        self.packed = torch.empty(max_rows, 4, **f32)
-        self._params = torch.empty(4, max_rows, **f32)  # inverse temperatures, uniforms, top_p, min_p: one upload
+        super().__init__(int(vocab), device, int(max_rows), draw_limits=True)
+        self.block_values, self.block_sums = self._f32(self.max_rows, self.nblocks), self._f32(self.max_rows, self.nblocks)
+        self.packed = self._f32(self.max_rows, 4)
+        self._params = self._f32(4, self.max_rows)  # inverse temperatures, uniforms, top_p, min_p: one upload
         vp, i, ll = C.c_void_p, C.c_int, C.c_int64
         self._many = _lib.sym("core", "mrs_nucleus_large_f32_packed_batched", [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, ll])
 
@@ -239,21 +248,9 @@ class Nucleus:
         """logits f32 [vocab] or [rows, vocab] (contiguous, on the device); temperature: positive and finite; uniforms: one value in [0, 1) per row; top_p / min_p: a
         float or one per row.  Returns the packed rows [rows, 4] = (token id, logprob under the full softmax, threshold logit x*, kept share of the mass) on the
         device (a view of this object's buffer: consume it before the next call)."""
-        x = logits.reshape(-1, self.vocab) if logits.dim() > 1 else logits.reshape(1, self.vocab)
-        rows = x.shape[0]
-        if x.dtype != torch.float32 or not x.is_contiguous() or rows > self.max_rows:
-            raise ValueError("nucleus: logits must be contiguous f32 with at most max_rows rows")
-        temps = np.broadcast_to(np.asarray(temperature, dtype=np.float64), (rows,))
-        if not np.all(np.isfinite(temps) & (temps > 0)):
-            raise ValueError("nucleus requires a positive finite temperature")
-        u = np.asarray(uniforms, dtype=np.float32).reshape(-1)
-        if u.shape[0] != rows or not np.all((u >= 0) & (u < 1)):
-            raise ValueError("nucleus requires one uniform in [0, 1) per row")
-        tp = np.broadcast_to(np.asarray(top_p, dtype=np.float32), (rows,))
-        mp = np.broadcast_to(np.asarray(min_p, dtype=np.float32), (rows,))
-        params = np.stack([(1.0 / temps).astype(np.float32), u, tp, mp])
-        self._params[:, :rows].copy_(torch.from_numpy(params), non_blocking=False)
-        pr = [self._params[j].data_ptr() for j in range(4)]
+        x, rows = self._rows(logits)
+        cuts = [np.broadcast_to(np.asarray(c, dtype=np.float32), (rows,)) for c in (top_p, min_p)]
+        pr = self._upload([self._inv_temperatures(temperature, rows), self._uniforms(uniforms, rows), *cuts], rows)
         self._many(x.data_ptr(), pr[0], pr[1], pr[2], pr[3], self.block_values.data_ptr(), self.block_sums.data_ptr(), self.packed.data_ptr(), rows, self.vocab,
                    CHUNK_SIZE, self.nblocks, torch.cuda.current_stream().cuda_stream)
         return self.packed[:rows]
@@ -279,17 +276,12 @@ def nucleus_host(logits_row, inv_temperature, uniform, top_p=1.0, min_p=0.0):
     """The contract of `mrs_nucleus_large_f32_packed_batched` for one row in numpy: (token, logprob, x*, kept share).  f32 weights, integer masses
     q_i = floor(w_i * 2^39); top-p keeps every logit >= x*, the largest logit at which the mass of the strictly greater logits is still below top_p * sum q (ALL ties
     at x* are kept); min-p keeps w_i > min_p; the draw inverts the cumulative kept mass in token order at min(floor(u * K), K - 1).  Raises where the device reports NaNs."""
-    x, inv_t, u = np.asarray(logits_row, dtype=np.float32).reshape(-1), np.float32(inv_temperature), np.float32(uniform)
-    tp, mp = np.float32(top_p), np.float32(min_p)
-    with np.errstate(over="ignore", invalid="ignore"):
-        gmax = np.float32(x.max() * inv_t) if x.size else np.float32(np.nan)
-        ok = np.isfinite(inv_t) and inv_t > 0 and np.isfinite(u) and 0 <= u < 1 and np.isfinite(gmax)
-        if ok:
-            w = np.exp((x * inv_t - gmax).astype(np.float32), dtype=np.float32)
-            denom = w.sum(dtype=np.float32)  # numpy's pairwise f32 sum: as close to the exact sum as the device's chunked trees
-            ok = np.isfinite(denom) and denom > 0
-    if not ok:
+    x, inv_t, u, gmax, w = _host_weights(logits_row, inv_temperature, uniform)
+    if w is not None:
+        denom = w.sum(dtype=np.float32)  # numpy's PAIRWISE f32 sum: as close to the exact sum as the device's chunked trees (categorical_host: sequential)
+    if w is None or not (np.isfinite(denom) and denom > 0):
         raise ValueError("invalid batched nucleus output")
+    tp, mp = np.float32(top_p), np.float32(min_p)
     q = (w.astype(np.float64) * NUCLEUS_SCALE).astype(np.uint64)  # exact: a power-of-two scale, then truncation
     total = int(q.sum(dtype=np.uint64))
     keep = np.ones(x.size, dtype=bool)
@@ -329,8 +321,8 @@ def generate(model, prompt, max_new_tokens: int, top_k: int, temperature: float 
         if cuts and not full_vocab_cuts:
             raise ValueError("sampling with top_p / min_p needs top_k >= 1 (the device categorical draw takes the whole row)")
         k, t1, tk = 0, None, None
-        cat = None if cuts else Categorical(vocab, model.device)
-        nuc = Nucleus(vocab, model.device) if cuts else None
+        draw = Nucleus(vocab, model.device) if cuts else Categorical(vocab, model.device)
+        parse, extra = (nucleus_token, (top_p, min_p)) if cuts else (categorical_token, ())
     else:
         k = min(int(top_k), vocab)
         t1 = Top1(vocab, model.device) if k == 1 else None
@@ -341,11 +333,8 @@ def generate(model, prompt, max_new_tokens: int, top_k: int, temperature: float 
     for i in range(max_new_tokens):
         if hasattr(model, "p2p_sync_error") and model.p2p_sync_error():  # tensor parallel: a timed-out peer-mailbox sum is NaN -- never hand out a token from it
             raise RuntimeError("p2p all-reduce timed out: the route has been dropped on every rank (RCCL from now on); re-run the request")
-        if k == 0 and nuc is not None:
-            tok, lp = nucleus_token(nuc(logits.contiguous(), temperature, [uniform_for(seed, i)], top_p, min_p).cpu().numpy()[0])
-            p = min(1.0, float(np.exp(lp)))
-        elif k == 0:
-            tok, lp = categorical_token(cat(logits.contiguous(), temperature, [uniform_for(seed, i)]).cpu().numpy()[0])
+        if k == 0:  # one launch pair of the whole-row draw in use, (token, logprob) parsed from its packed row
+            tok, lp = parse(draw(logits.contiguous(), temperature, [uniform_for(seed, i)], *extra).cpu().numpy()[0])
             p = min(1.0, float(np.exp(lp)))
         elif k == 1:  # sample_cuda_top1_row (sampler.rs:767-781): the arg-max, no temperature, logprob 0 (probability 1)
             tok, p = top1_token(t1(logits.contiguous()).cpu().numpy()[0]), 1.0

@@ -301,8 +301,7 @@ class PagedEngine:
         self.m, self.s = model, scheduler
         self.cfg = model.cfg
         self.steps = {"prompt": 0, "completion": 0, "preemptions": 0}
-        self._cat = None  # sampler.Categorical, made at the first sampled token
-        self._nuc = None  # sampler.Nucleus, made at the first token drawn under a top_p / min_p cut
+        self._draws = {}  # sampler.Categorical / sampler.Nucleus workspaces, each made at the first token drawn through it
 
     def _table(self, seq: Sequence):
         import torch
@@ -331,31 +330,26 @@ class PagedEngine:
         sampled = [i for i, s in enumerate(seqs) if s.temperature is not None and not cuts(s)]
         cut = [i for i, s in enumerate(seqs) if s.temperature is not None and cuts(s)]  # ONE nucleus launch with per-row top_p / min_p, 4 floats per row
         drawn = {}
-        pick = lambda idx: logits[idx[0]: idx[0] + 1] if len(idx) == 1 else logits[torch.tensor(idx, device=logits.device)]
-        if sampled:
-            us = [sampler.uniform_for(seqs[i].seed, len(seqs[i].generated)) for i in sampled]
+
+        def draw(idx, workspace, host_rule, parse, *per_row):
+            """one group of rows: the uniforms, then the host rule row by row on a CPU runner or ONE launch of the lazily made workspace; `per_row`: further lists"""
+            us = [sampler.uniform_for(seqs[i].seed, len(seqs[i].generated)) for i in idx]
             if self.m.device.type == "cpu":  # host runners: the same rule in numpy
-                for i, u in zip(sampled, us):
-                    drawn[i] = sampler.categorical_host(logits[i].float().numpy(), np.float32(1.0 / seqs[i].temperature), u)
-            else:
-                if self._cat is None:
-                    self._cat = sampler.Categorical(self.cfg.vocab_size, self.m.device, max_rows=max(8, self.cfg.max_batch))
-                packed = self._cat(pick(sampled).float().contiguous(), [seqs[i].temperature for i in sampled], us).cpu().numpy()
-                for r, i in enumerate(sampled):
-                    drawn[i] = sampler.categorical_token(packed[r])
+                for i, u, *extra in zip(idx, us, *per_row):
+                    drawn[i] = host_rule(logits[i].float().numpy(), np.float32(1.0 / seqs[i].temperature), u, *extra)[:2]
+                return
+            if workspace not in self._draws:
+                self._draws[workspace] = workspace(self.cfg.vocab_size, self.m.device, max_rows=max(8, self.cfg.max_batch))
+            rows = logits[idx[0]: idx[0] + 1] if len(idx) == 1 else logits[torch.tensor(idx, device=logits.device)]
+            packed = self._draws[workspace](rows.float().contiguous(), [seqs[i].temperature for i in idx], us, *per_row).cpu().numpy()
+            for r, i in enumerate(idx):
+                drawn[i] = parse(packed[r])
+
+        if sampled:
+            draw(sampled, sampler.Categorical, sampler.categorical_host, sampler.categorical_token)
         if cut:
-            us = [sampler.uniform_for(seqs[i].seed, len(seqs[i].generated)) for i in cut]
-            tps = [seqs[i].top_p if sampler.cut_active(seqs[i].top_p) else 1.0 for i in cut]
-            mps = [seqs[i].min_p if sampler.cut_active(seqs[i].min_p) else 0.0 for i in cut]
-            if self.m.device.type == "cpu":
-                for i, u, tp, mp in zip(cut, us, tps, mps):
-                    drawn[i] = sampler.nucleus_host(logits[i].float().numpy(), np.float32(1.0 / seqs[i].temperature), u, tp, mp)[:2]
-            else:
-                if self._nuc is None:
-                    self._nuc = sampler.Nucleus(self.cfg.vocab_size, self.m.device, max_rows=max(8, self.cfg.max_batch))
-                packed = self._nuc(pick(cut).float().contiguous(), [seqs[i].temperature for i in cut], us, tps, mps).cpu().numpy()
-                for r, i in enumerate(cut):
-                    drawn[i] = sampler.nucleus_token(packed[r])
+            draw(cut, sampler.Nucleus, sampler.nucleus_host, sampler.nucleus_token,
+                 [seqs[i].top_p if sampler.cut_active(seqs[i].top_p) else 1.0 for i in cut], [seqs[i].min_p if sampler.cut_active(seqs[i].min_p) else 0.0 for i in cut])
         for i, seq in enumerate(seqs):
             if i in drawn:
                 seq.logprobs.append(drawn[i][1])

@@ -193,11 +193,62 @@ def check_many_chunks(be, rows):
     assert np.array_equal(bv[0].view(np.uint32), x.view(np.uint32)) and np.all(bs == 1.0)
 
 
+# ---------------------------------------------------------------- D. stage 1 is ONE piece of arithmetic behind three entry points
+STAGE1_SHAPES = [(300, 64), (700, 256), (4101, 4096)]
+# (300, 64): five chunks, a ragged last one, most threads idle; (700, 256): a chunk exactly one thread stride wide; (4101, 4096): all 16 registers per thread, then a
+# 5-token tail chunk
+
+
+def check_stage1_shared(be, n, chunk):
+    """top-k (k = 1), the categorical draw and the nucleus draw leave the SAME chunk sums and chunk maxima for the same logits and temperatures, bit for bit: the
+    normaliser of all three is one computation.  No NaN (the two families report a NaN chunk's maximum differently by contract) and no chunk maximum of +-0 (the
+    key route and fmaxf may legitimately differ in its sign)."""
+    rows, nb = 2, (n + chunk - 1) // chunk
+    x = (np.random.default_rng(n).standard_normal((rows, n)) * 3).astype(np.float32)
+    for r in range(rows):  # one chunk of nothing but -inf per row, another chunk in each
+        b = (1 + r) % nb
+        x[r, b * chunk:(b + 1) * chunk] = NINF
+    pad = np.full((rows, nb * chunk), NINF, np.float32)
+    pad[:, :n] = x
+    assert not np.any(pad.reshape(rows, nb, chunk).max(axis=2) == 0)
+    inv_t = (1.0 / np.array([0.7, 1.3])).astype(np.float32)
+    us = np.array([0.25, 0.75], np.float32)
+    ws = lambda per_row: be.buf(np.full(rows * per_row, 7.0, np.float32))
+    xb, tb, ub = be.buf(x), be.buf(inv_t), be.buf(us)
+    k_bv, k_bi, k_bm, k_bs, k_pk = ws(nb), be.buf(np.zeros(rows * nb, np.uint32)), ws(nb), ws(nb), ws(4)
+    be.sym("topk_large_f32_packed_batched", [VP] * 7 + [I] * 5 + [LL])(xb.ptr, tb.ptr, k_bv.ptr, k_bi.ptr, k_bm.ptr, k_bs.ptr, k_pk.ptr, rows, n, 1, chunk, nb,
+                                                                       be.stream or 0)
+    c_bv, c_bs, c_pk = ws(nb), ws(nb), ws(2)
+    be.sym("categorical_large_f32_packed_batched", [VP] * 6 + [I] * 4 + [LL])(xb.ptr, tb.ptr, ub.ptr, c_bv.ptr, c_bs.ptr, c_pk.ptr, rows, n, chunk, nb, be.stream or 0)
+    n_bv, n_bs, n_pk = ws(nb), ws(nb), ws(4)
+    pb, mb = be.buf(np.full(rows, 0.9, np.float32)), be.buf(np.zeros(rows, np.float32))
+    be.sym("mrs_nucleus_large_f32_packed_batched", [VP] * 8 + [I] * 4 + [LL])(xb.ptr, tb.ptr, ub.ptr, pb.ptr, mb.ptr, n_bv.ptr, n_bs.ptr, n_pk.ptr, rows, n, chunk, nb,
+                                                                              be.stream or 0)
+    bits = lambda b: np.ascontiguousarray(b.numpy(), dtype=np.float32).reshape(rows, nb).view(np.uint32)
+    assert np.isfinite(c_pk.numpy()).all() and np.isfinite(n_pk.numpy()).all()  # every launch ran
+    assert np.array_equal(bits(k_bs), bits(c_bs)) and np.array_equal(bits(c_bs), bits(n_bs))
+    scaled = (c_bv.numpy().reshape(rows, nb).astype(np.float32) * inv_t[:, None]).astype(np.float32)
+    assert np.array_equal(scaled.view(np.uint32), bits(k_bm))
+    assert np.array_equal(bits(n_bv), bits(c_bv))
+
+
 # ---------------------------------------------------------------- the two backends
 @pytest.fixture(scope="module")
 def host():
     from tests.abi_backends import HostBackend
     return HostBackend()
+
+
+@pytest.mark.parametrize("n,chunk", STAGE1_SHAPES, ids=[f"n{s[0]}c{s[1]}" for s in STAGE1_SHAPES])
+def test_stage1_shared_host_emulation(host, n, chunk):
+    check_stage1_shared(host, n, chunk)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,chunk", STAGE1_SHAPES, ids=[f"n{s[0]}c{s[1]}" for s in STAGE1_SHAPES])
+def test_stage1_shared_gpu(dev, n, chunk):
+    from tests.abi_backends import GpuBackend
+    check_stage1_shared(GpuBackend(dev), n, chunk)
 
 
 def test_exact_cases_host_emulation(host):
