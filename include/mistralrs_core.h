@@ -94,6 +94,18 @@ void apply_sparse_penalties_f32(const void *x, void *dst, const uint32_t *token_
                                 float presence_penalty, float repetition_penalty, int64_t stream);
 void apply_sparse_logits_bias_f32(const void *x, void *dst, const uint32_t *token_ids, const float *biases, int n, int n_tokens, int64_t stream);
 
+/* The same pre-processing for every row of a step in ONE launch, from the raw token history (this library's own symbol: the reference has no batched device plan for a
+ * request with penalties, sampler.rs:617-631).  Row r's context is ctx_tokens[ctx_offsets[r] .. ctx_offsets[r + 1]); a token counts as generated iff its position in
+ * that context is >= min(prompt_lens[r], length).  With g = generated occurrences and s = all occurrences of a token: v = x; g > 0: v -= fmaf(g, frequency, presence);
+ * s > 0 and repetition != 1: v = v > 0 ? v / repetition : v * repetition; listed in bias_ids[bias_offsets[r] .. bias_offsets[r + 1]): v += bias -- bit for bit the chain
+ * apply_sparse_penalties_f32(generated counts, f, p, 1) -> apply_sparse_penalties_f32(all counts, 0, 0, rp) -> apply_sparse_logits_bias_f32 (sampler.rs:1111-1145).
+ * Token ids >= ncols are ignored; bias ids are unique within a row; bias_offsets == NULL: no bias.  x == dst is allowed.  The device counts with integer LDS atomics only,
+ * so dst is a function of the row's inputs alone.  Grid (ceil(ncols / chunk_size), nrows): returns without launching on nrows <= 0 or > 65535, ncols <= 0, or a
+ * chunk_size outside 1..4096. */
+void mrs_penalties_f32_batched(const float *x, float *dst, const uint32_t *ctx_tokens, const int32_t *ctx_offsets, const int32_t *prompt_lens,
+                               const float *frequency_penalties, const float *presence_penalties, const float *repetition_penalties, const uint32_t *bias_ids,
+                               const float *bias_values, const int32_t *bias_offsets, int nrows, int ncols, int chunk_size, int64_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,5 +1,6 @@
 // sampling.hip -- libmistralrscuda, sampling subset.  A MAP of this file: three two-stage families over rows of 100k+ f32 logits, the helpers they share, and the
-// arithmetic each helper pins.  (Further down, apart from all this: the sparse penalties / bias pre-processing.)  The caller owns every buffer.
+// arithmetic each helper pins.  (Further down, apart from all this: the sparse penalties / bias pre-processing,
+// one row at a time as the reference exports it, and mrs_penalties_f32_batched, every row of a step in one launch from the raw token history.)  The caller owns every buffer.
 //
 // The families -- stage 1 is one workgroup of NT threads per `chunk_size` logits, stage 2 one workgroup per row; the row is always a block index:
 //   top-k        topk_large_f32, topk_large_f32_packed, topk_large_f32_packed_batched      mistralrs-core/src/cuda/sort.cu:1502-1823,2146-2206 ; ffi.rs:583-624 ;
@@ -863,6 +864,94 @@ __global__ void __launch_bounds__(NT) sparse_bias_kernel(float *__restrict__ log
   logits[token_id] += biases[idx];  // token ids are unique in the caller's map (sampler.rs:1145-1160), as in the reference
 }
 
+// ---------------------------------------------------------------- the same pre-processing for ALL rows of a step in one launch: mrs_penalties_f32_batched (no reference
+// counterpart: cuda_batch_sampling_plan gives up on a request with penalties, sampler.rs:617-631, and the single-row chain above costs a host hash map, uploads and up to
+// three copy + update launch pairs per sequence and token, sampler.rs:1090-1169).  The launch takes the RAW token history of every row; counting and de-duplication happen here.
+//   grid (chunks, rows), one workgroup per `chunk_size` logits of one row, the chunk in registers in load_chunk's assignment -- a logit is read, updated and stored by its
+//   ONE owning thread, so x == dst is allowed;
+//   the workgroup streams the row's whole context (L2-resident, re-read by every workgroup of the row: len * 4 bytes against chunk_size * 8 bytes of logits traffic) and
+//   counts the tokens that fall in its chunk with integer LDS atomics: s_gen = occurrences at positions >= min(prompt_len, len), s_all = all occurrences;
+//   the row's bias list is scanned the same way: s_bias[local] = 1 + the entry's index (ids are unique within a row: plain stores);
+//   after one barrier: v = x; g > 0: v -= fmaf(g, f, p); s > 0 and rp != 1: v = v > 0 ? v / rp : v * rp; listed: v += bias -- the expressions of sparse_penalties_kernel and
+//   sparse_bias_kernel, so dst equals the chain penalties(generated counts, f, p, 1) -> penalties(all counts, 0, 0, rp) -> bias bit for bit (sampler.rs:1111-1145).
+// Integer atomics only, nothing crosses a workgroup: dst is a function of the row's inputs alone, whatever the launch, the batch row or the neighbours are.
+struct PenArgs {
+  const float *x;
+  float *dst;
+  const uint32_t *ctx_tokens;
+  const int32_t *ctx_offsets, *prompt_lens;
+  const float *frequency_penalties, *presence_penalties, *repetition_penalties;
+  const uint32_t *bias_ids;
+  const float *bias_values;
+  const int32_t *bias_offsets;  // NULL: no bias in this launch
+  int ncols, chunk_size;
+};
+constexpr int PEN_UNROLL = 4;  // context loads in flight per thread
+
+__global__ void __launch_bounds__(NT) penalties_batched_kernel(PenArgs a) {
+  __shared__ int s_gen[NT * MAXV], s_all[NT * MAXV], s_bias[NT * MAXV];
+  const int tid = threadIdx.x;
+  const size_t row = blockIdx.y;
+  const long long start = (long long)blockIdx.x * a.chunk_size, left = (long long)a.ncols - start;
+  const int width = left <= 0 ? 0 : (left < a.chunk_size ? (int)left : a.chunk_size);
+  const float *x = a.x + row * (size_t)a.ncols + start;
+  float *dst = a.dst + row * (size_t)a.ncols + start;
+  const int c0 = a.ctx_offsets[row], len = max(0, a.ctx_offsets[row + 1] - c0);
+  const int b0 = a.bias_offsets ? a.bias_offsets[row] : 0, nbias = a.bias_offsets ? max(0, a.bias_offsets[row + 1] - b0) : 0;
+  float v[MAXV];
+  load_chunk(x, width, v);  // in flight while the context is counted
+  if (len > 0 || nbias > 0) {  // uniform over the workgroup
+    for (int i = tid; i < a.chunk_size; i += NT) {
+      s_gen[i] = 0;
+      s_all[i] = 0;
+      if (nbias > 0) s_bias[i] = 0;
+    }
+    __syncthreads();
+    const uint32_t *ctx = a.ctx_tokens + c0;
+    const int gen_from = min(a.prompt_lens[row], len);  // positions from here on were generated
+    for (int base = tid; base < len; base += PEN_UNROLL * NT) {
+      uint32_t t[PEN_UNROLL];
+#pragma unroll
+      for (int j = 0; j < PEN_UNROLL; ++j) t[j] = base + j * NT < len ? ctx[base + j * NT] : 0xffffffffu;
+#pragma unroll
+      for (int j = 0; j < PEN_UNROLL; ++j) {
+        const int pos = base + j * NT;
+        const long long local = (long long)t[j] - start;  // ids >= ncols fall outside every chunk: ignored
+        if (pos < len && local >= 0 && local < width) {
+          atomicAdd(&s_all[local], 1);
+          if (pos >= gen_from) atomicAdd(&s_gen[local], 1);
+        }
+      }
+    }
+    for (int e = tid; e < nbias; e += NT) {
+      const long long local = (long long)a.bias_ids[b0 + e] - start;
+      if (local >= 0 && local < width) s_bias[local] = e + 1;
+    }
+    __syncthreads();
+    const float f = a.frequency_penalties[row], p = a.presence_penalties[row], rp = a.repetition_penalties[row];
+#pragma unroll
+    for (int j = 0; j < MAXV; ++j) {
+      const int local = tid + j * NT;
+      if (local < width) {
+        const int g = s_gen[local], s = s_all[local];
+        float value = v[j];
+        if (g > 0) value -= fmaf((float)g, f, p);  // one rounding, as sparse_penalties_kernel
+        if (s > 0 && rp != 1.0f) value = value > 0.0f ? value / rp : value * rp;
+        if (nbias > 0) {
+          const int e = s_bias[local];
+          if (e > 0) value += a.bias_values[b0 + e - 1];
+        }
+        v[j] = value;
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < MAXV; ++j) {
+    const int local = tid + j * NT;
+    if (local < width) dst[local] = v[j];
+  }
+}
+
 }  // namespace sampling
 }  // namespace mrs
 
@@ -916,5 +1005,15 @@ extern "C" void apply_sparse_logits_bias_f32(const void *x, void *dst, const uin
   hipLaunchKernelGGL(copy_f32_kernel, dim3((n + NT * 4 - 1) / (NT * 4)), dim3(NT), 0, s, (const float *)x, (float *)dst, n);
   if (n_tokens <= 0) return;
   hipLaunchKernelGGL(sparse_bias_kernel, dim3((n_tokens + NT - 1) / NT), dim3(NT), 0, s, (float *)dst, token_ids, biases, n, n_tokens);
+}
+extern "C" void mrs_penalties_f32_batched(const float *x, float *dst, const uint32_t *ctx_tokens, const int32_t *ctx_offsets, const int32_t *prompt_lens,
+                                          const float *frequency_penalties, const float *presence_penalties, const float *repetition_penalties,
+                                          const uint32_t *bias_ids, const float *bias_values, const int32_t *bias_offsets, int nrows, int ncols, int chunk_size,
+                                          int64_t stream) {
+  using namespace mrs::sampling;
+  if (nrows <= 0 || nrows > 65535 || ncols <= 0 || chunk_size < 1 || chunk_size > NT * MAXV) return;  // the rows are a grid dimension
+  PenArgs a{x, dst, ctx_tokens, ctx_offsets, prompt_lens, frequency_penalties, presence_penalties, repetition_penalties, bias_ids, bias_values, bias_offsets, ncols,
+            chunk_size};
+  hipLaunchKernelGGL(penalties_batched_kernel, dim3((unsigned)(((long long)ncols + chunk_size - 1) / chunk_size), nrows), dim3(NT), 0, (hipStream_t)stream, a);
 }
 

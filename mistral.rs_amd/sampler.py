@@ -306,16 +306,172 @@ def nucleus_host(logits_row, inv_temperature, uniform, top_p=1.0, min_p=0.0):
     return tok, lp, float(xstar), float(np.float32(np.float64(kept) / np.float64(total)))
 
 
+MAX_BIAS = 1024  # logit-bias entries per row that a `Penalties` workspace has room for
+
+
+def _f32_or(v, default):
+    with np.errstate(over="ignore"):
+        return np.float32(default if v is None else v)
+
+
+def _token_ids(tokens, what):
+    """token ids as uint32; refuses negative, non-integer and > 32-bit ids"""
+    try:
+        a = np.asarray(list(tokens) if not isinstance(tokens, np.ndarray) else tokens)
+        a = a.reshape(-1) if a.size else np.zeros(0, np.int64)
+        ok = a.dtype.kind in "iuf" and bool(np.all(np.isfinite(a) & (a >= 0) & (a < 2 ** 32) & (a == np.floor(a))))
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"penalties: {what} must be non-negative integer token ids")
+    return a.astype(np.uint32)
+
+
+def check_penalties(frequency_penalty=None, presence_penalty=None, repetition_penalty=None, logit_bias=None):
+    """The refusals that `Penalties`, `penalties_host` and the engine share (None: the inactive default).  Returns the f32 triple and the bias as (ids uint32, values f32)
+    with the zero entries dropped (sampler.rs:1153-1158 drops them too)."""
+    f, p, rp = _f32_or(frequency_penalty, 0.0), _f32_or(presence_penalty, 0.0), _f32_or(repetition_penalty, 1.0)
+    if not (np.isfinite(f) and np.isfinite(p) and np.isfinite(rp)):
+        raise ValueError("penalties: frequency, presence and repetition penalty must be finite")
+    if rp <= 0:
+        raise ValueError("penalties: repetition_penalty must be > 0")
+    if logit_bias is None:
+        logit_bias = {}
+    if not isinstance(logit_bias, dict):
+        raise ValueError("penalties requires logit_bias as a dict {token id: bias}")
+    ids = _token_ids(list(logit_bias.keys()), "logit_bias keys")
+    try:
+        with np.errstate(over="ignore"):
+            vals = np.asarray(list(logit_bias.values()), dtype=np.float64).astype(np.float32).reshape(-1)
+    except (TypeError, ValueError):
+        raise ValueError("penalties: logit_bias values must be finite numbers") from None
+    if not np.all(np.isfinite(vals)):
+        raise ValueError("penalties: logit_bias values must be finite numbers")
+    if np.unique(ids).size != ids.size:
+        raise ValueError("penalties requires unique logit_bias token ids")
+    keep = vals != 0
+    if int(keep.sum()) > MAX_BIAS:
+        raise ValueError(f"penalties requires at most {MAX_BIAS} logit_bias entries per row")
+    return f, p, rp, ids[keep], vals[keep]
+
+
+def penalties_active(frequency_penalty, presence_penalty, repetition_penalty, logit_bias) -> bool:
+    """True iff the setting changes a row: f != 0, p != 0, rp != 1 or a non-zero bias entry; None is inactive (a NaN is active, and refused by check_penalties)"""
+    f, p, rp = frequency_penalty, presence_penalty, repetition_penalty
+    if (f is not None and float(f) != 0.0) or (p is not None and float(p) != 0.0) or (rp is not None and float(rp) != 1.0):
+        return True
+    return bool(logit_bias) and any(float(v) != 0.0 for v in logit_bias.values())
+
+
+class Penalties(_Workspace):
+    """Workspace + launcher of the batched pre-processing of rows of `vocab` f32 logits (`mrs_penalties_f32_batched`; the reference has no batched device plan for a request
+    with penalties, sampler.rs:617-631): frequency / presence penalties over the GENERATED tokens, the repetition penalty over the WHOLE context, then the additive bias
+    -- sampler.rs:1090-1169.  The raw token history goes up; the device counts.  One call = two uploads (int32 and f32 parameters) + one launch."""
+    NAME = NOUN = "penalties"
+
+    def __init__(self, vocab: int, device, max_rows: int = 1, max_context: int = 1 << 16):
+        super().__init__(int(vocab), device, int(max_rows))
+        if self.max_rows < 1 or self.max_rows > 65535:  # the rows are a grid dimension
+            raise ValueError(f"penalties: max_rows={max_rows} must be in [1, 65535]")
+        if int(max_context) < 0:
+            raise ValueError(f"penalties: max_context={max_context} must not be negative")
+        self.max_context = int(max_context)
+        self.dst = self._f32(self.max_rows, self.vocab)
+        # int32: context offsets [rows + 1], prompt lengths [rows], bias offsets [rows + 1], bias ids, context tokens; f32: the three penalties [rows] each, bias values
+        self._ints = torch.empty(3 * self.max_rows + 2 + self.max_rows * MAX_BIAS + self.max_context, dtype=torch.int32, device=device)
+        self._floats = self._f32(3 * self.max_rows + self.max_rows * MAX_BIAS)
+        vp, i, ll = C.c_void_p, C.c_int, C.c_int64
+        self._many = _lib.sym("core", "mrs_penalties_f32_batched", [vp] * 11 + [i, i, i, ll])
+
+    def _per_row(self, v, default, rows):
+        try:
+            return np.broadcast_to(np.asarray(default if v is None else v, dtype=np.float64), (rows,))
+        except (TypeError, ValueError):
+            raise ValueError("penalties requires one penalty value per row, or one for all") from None
+
+    def __call__(self, logits: torch.Tensor, contexts, prompt_lens, frequency_penalty=0.0, presence_penalty=0.0, repetition_penalty=1.0, logit_bias=None) -> torch.Tensor:
+        """logits f32 [vocab] or [rows, vocab] (contiguous, on the device); contexts: one token-id sequence per row (prompt + generated so far, may be empty);
+        prompt_lens: how many leading tokens of each context are the prompt (an int, or one per row); the penalties: a float or one per row; logit_bias: a dict
+        {token id: bias} for all rows, or a list with one dict (or None) per row -- entries equal to 0 or with an id >= vocab are dropped.  Returns the updated rows
+        [rows, vocab] on the device (a view of this object's buffer: consume it before the next call); `logits` is left as it is."""
+        x, rows = self._rows(logits)
+        if not isinstance(contexts, (list, tuple)) or len(contexts) != rows or any(np.isscalar(c) for c in contexts):
+            raise ValueError("penalties requires one context (a sequence of token ids) per row")
+        ctx = [_token_ids(c, "context tokens") for c in contexts]
+        try:
+            pl = np.broadcast_to(np.asarray(prompt_lens), (rows,))
+            ok = pl.dtype.kind in "iu" and bool(np.all(pl >= 0))
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError("penalties requires one non-negative integer prompt length per row, or one for all")
+        biases = logit_bias if isinstance(logit_bias, (list, tuple)) else [logit_bias] * rows
+        if len(biases) != rows:
+            raise ValueError("penalties requires one logit_bias dict per row, or one for all")
+        fs, ps, rps = (self._per_row(v, d, rows) for v, d in ((frequency_penalty, 0.0), (presence_penalty, 0.0), (repetition_penalty, 1.0)))
+        par = [check_penalties(fs[r], ps[r], rps[r], biases[r]) for r in range(rows)]
+        bias = [(ids[ids < self.vocab], vals[ids < self.vocab]) for _, _, _, ids, vals in par]
+        offsets = np.concatenate([[0], np.cumsum([c.size for c in ctx])]).astype(np.int64)
+        if offsets[-1] > self.max_context:
+            raise ValueError(f"penalties: {int(offsets[-1])} context tokens exceed max_context={self.max_context}")
+        boffsets = np.concatenate([[0], np.cumsum([b[0].size for b in bias])]).astype(np.int64)
+        ints = np.concatenate([offsets, np.minimum(pl, 2 ** 31 - 1).astype(np.int64), boffsets, *[b[0] for b in bias], *ctx]).astype(np.uint32).view(np.int32)
+        floats = np.concatenate([[q[j] for q in par] for j in range(3)] + [b[1] for b in bias]).astype(np.float32)
+        self._ints[:ints.size].copy_(torch.from_numpy(ints), non_blocking=False)
+        self._floats[:floats.size].copy_(torch.from_numpy(floats), non_blocking=False)
+        ip, fp = self._ints.data_ptr(), self._floats.data_ptr()
+        at = lambda base, n: base + 4 * n
+        has_bias = boffsets[-1] > 0
+        self._many(x.data_ptr(), self.dst.data_ptr(), at(ip, 3 * rows + 2 + int(boffsets[-1])), ip, at(ip, rows + 1), fp, at(fp, rows), at(fp, 2 * rows),
+                   at(ip, 3 * rows + 2) if has_bias else None, at(fp, 3 * rows) if has_bias else None, at(ip, 2 * rows + 1) if has_bias else None,
+                   rows, self.vocab, CHUNK_SIZE, torch.cuda.current_stream().cuda_stream)
+        return self.dst[:rows]
+
+
+def penalties_host(logits_row, context, prompt_len, frequency_penalty=0.0, presence_penalty=0.0, repetition_penalty=1.0, logit_bias=None):
+    """The contract of `mrs_penalties_f32_batched` for one row in numpy f32: the updated row.  With g = occurrences of a token among context[prompt_len:] and s = its
+    occurrences in the whole context: v = x; g > 0: v -= g * f + p; s > 0 and rp != 1: v = v > 0 ? v / rp : v * rp; then v += bias.  Token ids >= the row's length are
+    ignored; bias entries equal to 0 are dropped.
+    The device evaluates g * f + p as ONE fused multiply-add; here it is a float64 product and sum rounded once to f32.  The float64 sum is exact -- and this rule equal to
+    the device BIT FOR BIT -- whenever the counts are <= 4096 and each penalty is 0 or has a magnitude in [2^-10, 8]: the product then has at most 13 + 24 - 1 = 36
+    significant bits and the two terms together span fewer than 53."""
+    x = np.array(logits_row, dtype=np.float32).reshape(-1)
+    n = x.size
+    f, p, rp, ids, vals = check_penalties(frequency_penalty, presence_penalty, repetition_penalty, logit_bias)
+    ctx = _token_ids(context, "context tokens")
+    if not isinstance(prompt_len, (int, np.integer)) or prompt_len < 0:
+        raise ValueError("penalties requires one non-negative integer prompt length per row, or one for all")
+    gen = ctx[min(int(prompt_len), ctx.size):]
+    g = np.bincount(gen[gen < n], minlength=n)
+    s = np.bincount(ctx[ctx < n], minlength=n)
+    with np.errstate(over="ignore", invalid="ignore"):
+        hit = g > 0
+        x[hit] = x[hit] - (g[hit].astype(np.float64) * np.float64(f) + np.float64(p)).astype(np.float32)
+        if rp != np.float32(1.0):
+            hit = s > 0
+            v = x[hit]
+            x[hit] = np.where(v > 0, v / rp, v * rp)
+        ids, vals = ids[ids < n], vals[ids < n]
+        x[ids] = x[ids] + vals
+    return x
+
+
 def generate(model, prompt, max_new_tokens: int, top_k: int, temperature: float = 1.0, top_p: float = 1.0, min_p: float = 0.0, seed: int = 0,
-             full_vocab_cuts: bool = False):
+             full_vocab_cuts: bool = False, frequency_penalty: float = 0.0, presence_penalty: float = 0.0, repetition_penalty: float = 1.0, logit_bias=None):
     """Sampled decoding on a `Llama` runner (the loop of `Sampler::sample`, sampler.rs:1262-1290): prefill, then per token one decode step and
       top_k >= 2: the device top-k over the logits row, `2k + 2` floats to the host, the top-p / min-p cuts and the draw there;
       top_k == 1: the arg-max through the top-1 kernels, no temperature, probability 1 (sample_cuda_top1_row);
       top_k <= 0 or None (top_p and min_p inactive): the device categorical draw over the whole row at `uniform_for(seed, i)` -- one launch pair, 2 floats to the host,
                  probability exp(logprob).  With an active top_p or min_p: `full_vocab_cuts=True` draws through `Nucleus` (the cuts over the WHOLE vocabulary on the
                  device, 4 floats to the host); without the keyword this raises, as the reference leaves the device there.
+    With an active penalty or logit bias (`penalties_active`) the row first goes through `Penalties` -- context = prompt + tokens so far, the prompt's tokens not
+    "generated" -- and the updated row takes the place of the raw one in all three modes (the reference applies them before everything else, sampler.rs:1853).
     Returns (tokens, reporting probabilities)."""
     vocab = int(model.cfg.vocab_size)
+    pen = None
+    if penalties_active(frequency_penalty, presence_penalty, repetition_penalty, logit_bias):
+        check_penalties(frequency_penalty, presence_penalty, repetition_penalty, logit_bias)
+        pen = Penalties(vocab, model.device, max_context=len(prompt) + max_new_tokens)
     if top_k is None or int(top_k) <= 0:
         cuts = 0.0 < top_p < 1.0 or 0.0 < min_p < 1.0
         if cuts and not full_vocab_cuts:
@@ -333,6 +489,8 @@ def generate(model, prompt, max_new_tokens: int, top_k: int, temperature: float 
     for i in range(max_new_tokens):
         if hasattr(model, "p2p_sync_error") and model.p2p_sync_error():  # tensor parallel: a timed-out peer-mailbox sum is NaN -- never hand out a token from it
             raise RuntimeError("p2p all-reduce timed out: the route has been dropped on every rank (RCCL from now on); re-run the request")
+        if pen is not None:
+            logits = pen(logits.contiguous(), [list(prompt) + toks], len(prompt), frequency_penalty, presence_penalty, repetition_penalty, logit_bias)
         if k == 0:  # one launch pair of the whole-row draw in use, (token, logprob) parsed from its packed row
             tok, lp = parse(draw(logits.contiguous(), temperature, [uniform_for(seed, i)], *extra).cpu().numpy()[0])
             p = min(1.0, float(np.exp(lp)))

@@ -48,6 +48,11 @@ class Sequence:
     logprobs: List[float] = field(default_factory=list)  # one entry per SAMPLED token (greedy tokens add none): under the FULL softmax, cuts or not
     top_p: Optional[float] = None         # a value strictly inside (0, 1) cuts the nucleus over the whole vocabulary (needs a temperature); anything else: no cut
     min_p: Optional[float] = None
+    # logits pre-processing before the arg-max or the draw (sampler.rs:1090-1169); None: inactive.  frequency / presence count the GENERATED tokens, repetition the whole context
+    frequency_penalty: Optional[float] = None
+    presence_penalty: Optional[float] = None
+    repetition_penalty: Optional[float] = None
+    logit_bias: Optional[dict] = None     # {token id: additive bias}
 
     def __post_init__(self):
         if not self.prompt_len:
@@ -106,9 +111,10 @@ class PagedAttentionScheduler:
 
     # ---- queue interface (Scheduler trait, scheduler.rs:1082-1110)
     def add_seq(self, seq: Sequence) -> None:
-        from .sampler import cut_active
+        from .sampler import check_penalties, cut_active
         if seq.temperature is None and (cut_active(seq.top_p) or cut_active(seq.min_p)):
             raise ValueError("top_p / min_p need a temperature: a greedy sequence takes the arg-max")
+        check_penalties(seq.frequency_penalty, seq.presence_penalty, seq.repetition_penalty, seq.logit_bias)  # penalties on a greedy sequence are fine (sampler.rs:1853)
         self._clock += 1
         if not seq.timestamp:
             seq.timestamp = self._clock
@@ -301,7 +307,7 @@ class PagedEngine:
         self.m, self.s = model, scheduler
         self.cfg = model.cfg
         self.steps = {"prompt": 0, "completion": 0, "preemptions": 0}
-        self._draws = {}  # sampler.Categorical / sampler.Nucleus workspaces, each made at the first token drawn through it
+        self._draws = {}  # sampler.Categorical / sampler.Nucleus / sampler.Penalties workspaces, each made at the first token that goes through it
 
     def _table(self, seq: Sequence):
         import torch
@@ -319,6 +325,10 @@ class PagedEngine:
         """The next token of every row of one launch (`logits[i]` belongs to `seqs[i]`): rows with a temperature are drawn TOGETHER -- one categorical launch pair over
         their logits with per-row inverse temperature and uniform, one copy of 2 floats per row; rows with an active top_p / min_p cut go TOGETHER through one nucleus
         launch (per-row cuts, 4 floats per row; `nucleus_host` on a CPU runner); greedy rows keep the arg-max.  A NaN row raises.
+        Before that, when a row of the launch carries an active penalty or logit bias: ONE `Penalties` launch over the rows of the step (context = seq.tokens, prompt
+        length = seq.prompt_len; a row without a setting rides along with an empty context, a plain copy), `penalties_host` row by row on a CPU runner; the updated
+        rows replace the raw ones as input of the arg-max and of both draws, so the logprobs are under the softmax of the penalized row.  `last_logits` stays the raw
+        model row.  A launch without such a row takes the path it took before: no extra launch, no extra copy.
         Tensor parallel: every rank holds the same logits after the all-reduce and derives the same uniforms from (seed, position), so every rank draws the
         same token without any further communication."""
         import torch
@@ -327,6 +337,22 @@ class PagedEngine:
         # add_seq refuses this at submission; the fields of a Sequence stay writable afterwards, and the engine is also driven without a scheduler
         if any(s.temperature is None and cuts(s) for s in seqs):
             raise ValueError("top_p / min_p need a temperature: a greedy sequence takes the arg-max")
+        setting = lambda s: (s.frequency_penalty, s.presence_penalty, s.repetition_penalty, s.logit_bias)
+        for s in seqs:
+            sampler.check_penalties(*setting(s))
+        pen = [i for i, s in enumerate(seqs) if sampler.penalties_active(*setting(s))]
+        raw = logits
+        if pen and self.m.device.type == "cpu":
+            logits = raw.float().clone()
+            for i in pen:
+                logits[i] = torch.from_numpy(sampler.penalties_host(raw[i].float().numpy(), seqs[i].tokens, seqs[i].prompt_len, *setting(seqs[i])))
+        elif pen:
+            if sampler.Penalties not in self._draws:
+                rows = max(8, self.cfg.max_batch)
+                self._draws[sampler.Penalties] = sampler.Penalties(self.cfg.vocab_size, self.m.device, max_rows=rows, max_context=rows * self.cfg.max_context_len)
+            col = lambda j, default: [default if setting(s)[j] is None else setting(s)[j] for s in seqs]
+            logits = self._draws[sampler.Penalties](raw.float().contiguous(), [s.tokens if i in pen else [] for i, s in enumerate(seqs)], [s.prompt_len for s in seqs],
+                                                    col(0, 0.0), col(1, 0.0), col(2, 1.0), [s.logit_bias for s in seqs])
         sampled = [i for i, s in enumerate(seqs) if s.temperature is not None and not cuts(s)]
         cut = [i for i, s in enumerate(seqs) if s.temperature is not None and cuts(s)]  # ONE nucleus launch with per-row top_p / min_p, 4 floats per row
         drawn = {}
@@ -353,9 +379,9 @@ class PagedEngine:
         for i, seq in enumerate(seqs):
             if i in drawn:
                 seq.logprobs.append(drawn[i][1])
-                self._finish_token(seq, logits[i], drawn[i][0])
-            else:
-                self._finish_token(seq, logits[i])
+                self._finish_token(seq, raw[i], drawn[i][0])
+            else:  # greedy: the arg-max of the (penalized) row
+                self._finish_token(seq, raw[i], int(logits[i].argmax()) if pen else None)
 
     def _p2p_guard(self) -> None:
         """Tensor parallel: before tokens are handed out, the per-rank error word of the peer-mailbox all-reduce is MAX-reduced over the ranks (Llama.p2p_sync_error);
