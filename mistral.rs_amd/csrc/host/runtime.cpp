@@ -12,7 +12,13 @@
 //   use_fused = 0 : the reference's launch sequence through the drop-in C-ABI symbols (launch_mmvq_*,
 //                   rotary_embedding_positions, reshape_and_cache, paged attention, add_rms_norm_*)
 //   use_fused = 1 : the MI355X fused kernels of ext_decode.hip (5 launches per layer)
-// The runner never allocates device memory: every buffer comes from the caller (mrs_llama_buffers).
+// Prompts (Llama::prefill) take ONE of three paths over one layout of the caller's prefill workspace (PrefillBufs), selected in this order:
+//   prefill_exact   : prefill_exact_ok() -- prefill mode 1 (or MRS_PREFILL_EXACT, default 1), the decode engine and an MFMA-order copy of every linear: the engine's
+//                     arithmetic, every logit and KV page == token-by-token decode
+//   prefill_shadow  : shadow_selected(T) -- T > prefill_big_min, mode != 2, dense model with a bf16 shadow copy of every linear, head_dim 128 / block 32: bf16 rows x
+//                     plain library GEMMs (hipBLASLt)
+//   prefill_dequant : otherwise -- fused block-dequant bf16 MFMA GEMMs on the GGUF blocks (f32 activations at T <= prefill_big_min, bf16 slabs above)
+// The runner never allocates device memory: every buffer comes from the caller (mrs_llama_buffers, mrs_llama_prefill_args.workspace).
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 
@@ -22,6 +28,7 @@
 #include <cmath>
 #include <cstring>
 #include <algorithm>
+#include <array>
 #include <initializer_list>
 #include <memory>
 #include <string>
@@ -169,7 +176,20 @@ struct Block {
   QTensor gate_exps, up_exps, down_exps;
   const float *input_layernorm = nullptr, *post_attention_layernorm = nullptr;
   void *key_cache = nullptr, *value_cache = nullptr;
+  // the seven dense linears in the fixed order q, k, v, o, gate, up, down (a MoE block has the first four only)
+  std::array<const GgufMatMul *, 7> dense() const { return {q_proj.get(), k_proj.get(), v_proj.get(), o_proj.get(), gate_proj.get(), up_proj.get(), down_proj.get()}; }
 };
+
+// Carves a caller's buffer: take(bytes) returns base + offset and advances by the 256-byte-aligned size.  A null base only counts, so the function that lays a
+// workspace out is also the one that sizes it (`off` after the last take).
+static size_t align(size_t v) { return (v + 255) & ~(size_t)255; }
+struct Arena {
+  char *base;
+  size_t off = 0;
+  explicit Arena(void *p) : base(p ? (char *)(((uintptr_t)p + 255) & ~(uintptr_t)255) : nullptr) {}
+  template <class T = void> T *take(size_t bytes) { T *r = base ? (T *)(base + off) : nullptr; off += align(bytes); return r; }
+};
+constexpr size_t WORKSPACE_SLACK = 4096;  // on top of every layout: covers the alignment of the caller's base
 
 struct Workspace {  // carve-up of the caller's scratch
   float *h, *xn, *q, *k, *v, *attn, *proj, *act;
@@ -213,59 +233,40 @@ class Llama {
     return mrs_comm_all_reduce_sum_f32(comm, buf, count, s);
   }
 
-  static size_t align(size_t v) { return (v + 255) & ~(size_t)255; }
-  static size_t workspace_bytes(const mrs_llama_config &c) {
-    const size_t B = c.max_batch, d = c.hidden_size, nq = (size_t)c.num_heads * c.head_dim, nkv = (size_t)c.num_kv_heads * c.head_dim;
-    const size_t ya = B * (pad_to((int)std::max(d, nq), MATRIX_ROW_PADDING) / 32) * 36;
-    const size_t yb = B * (pad_to(c.intermediate_size, MATRIX_ROW_PADDING) / 32) * 36;
+  // ---- the decode workspace, stated once: a null base sizes it (workspace_bytes), the caller's buffer carves it (set_buffers)
+  static size_t lay_out(const mrs_llama_config &c, void *base, Workspace &w) {
+    const size_t B = c.max_batch, d = c.hidden_size, nq = (size_t)c.num_heads * c.head_dim, nkv = (size_t)c.num_kv_heads * c.head_dim, ff = c.intermediate_size;
+    Arena a(base);
+    w.h = a.take<float>(B * d * 4); w.xn = a.take<float>(B * d * 4); w.proj = a.take<float>(B * d * 4);
+    w.q = a.take<float>(B * nq * 4); w.attn = a.take<float>(B * nq * 4);
+    w.k = a.take<float>(B * nkv * 4); w.v = a.take<float>(B * nkv * 4);
+    w.act = a.take<float>(B * ff * 4);
+    w.y_a_bytes = B * (pad_to((int)std::max(d, nq), MATRIX_ROW_PADDING) / 32) * 36;
+    w.y_b_bytes = B * (pad_to(c.intermediate_size, MATRIX_ROW_PADDING) / 32) * 36;
+    w.y_a = a.take(w.y_a_bytes); w.y_b = a.take(w.y_b_bytes);
     const size_t parts = (size_t)mrs_decode_attention_max_splits(c.max_context_len);  // >= the reference's 512-token partitions
-    size_t t = 0;
-    t += align(B * d * 4) * 3;            // h, xn, proj
-    t += align(B * nq * 4) * 2;           // q, attn
-    t += align(B * nkv * 4) * 2;          // k, v
-    t += align(B * (size_t)c.intermediate_size * 4);  // act
-    t += align(ya) + align(yb);
-    t += align(B * c.num_heads * parts * c.head_dim * 4) + 2 * align(B * c.num_heads * parts * 4);
-    t += align(B * 8);
-    t += align(mrs_dec_act_image_bytes((int)nq, (int)B)) + align(B * (size_t)c.num_kv_heads * 4);
-    t += align(mrs_dec_act_image_bytes(std::max((int)d, (int)c.intermediate_size), (int)std::min<size_t>(B, 8)));  // act_img
+    w.attn_ws = a.take(B * c.num_heads * parts * c.head_dim * 4);
+    w.exp_sums = a.take<float>(B * c.num_heads * parts * 4);
+    w.max_logits = a.take<float>(B * c.num_heads * parts * 4);
+    w.sample_scratch = a.take(B * 8);
+    w.attn_img = a.take(mrs_dec_act_image_bytes((int)nq, (int)B));
+    w.attn_ticket = a.take<unsigned>(B * (size_t)c.num_kv_heads * 4);
+    w.act_img = a.take(mrs_dec_act_image_bytes(std::max((int)d, (int)c.intermediate_size), (int)std::min<size_t>(B, 8)));
     if (c.num_experts > 0) {
       const size_t k = std::max(1, (int)c.num_experts_per_tok);
-      t += align(B * k * 4) * 2 + align(k * (pad_to(c.intermediate_size, MATRIX_ROW_PADDING) / 32) * 36);
-      t += align(k * (size_t)c.intermediate_size * 4);
-      t += align(mrs_moe_router_split_scratch_bytes((int)B, (int)c.num_experts));
+      w.moe_ids = a.take<int32_t>(B * k * 4); w.moe_w = a.take<float>(B * k * 4);
+      w.moe_y = a.take(k * (pad_to(c.intermediate_size, MATRIX_ROW_PADDING) / 32) * 36);
+      w.moe_act = a.take<float>(k * ff * 4);
+      w.moe_router_scratch = a.take(mrs_moe_router_split_scratch_bytes((int)B, (int)c.num_experts));
     }
-    return t + 4096;
+    return a.off;
   }
+  static size_t workspace_bytes(const mrs_llama_config &c) { Workspace w{}; return lay_out(c, nullptr, w) + WORKSPACE_SLACK; }
 
   int set_buffers(const mrs_llama_buffers &b) {
     if (b.workspace_bytes < workspace_bytes(cfg)) return fail("workspace too small: %zu < %zu", b.workspace_bytes, workspace_bytes(cfg));
     bufs = b;
-    const size_t B = cfg.max_batch, d = cfg.hidden_size, nq = (size_t)cfg.num_heads * cfg.head_dim, nkv = (size_t)cfg.num_kv_heads * cfg.head_dim;
-    char *p = (char *)(((uintptr_t)b.workspace + 255) & ~(uintptr_t)255);
-    auto take = [&](size_t n) { char *r = p; p += align(n); return r; };
-    ws.h = (float *)take(B * d * 4); ws.xn = (float *)take(B * d * 4); ws.proj = (float *)take(B * d * 4);
-    ws.q = (float *)take(B * nq * 4); ws.attn = (float *)take(B * nq * 4);
-    ws.k = (float *)take(B * nkv * 4); ws.v = (float *)take(B * nkv * 4);
-    ws.act = (float *)take(B * (size_t)cfg.intermediate_size * 4);
-    ws.y_a_bytes = B * (pad_to((int)std::max(d, nq), MATRIX_ROW_PADDING) / 32) * 36;
-    ws.y_b_bytes = B * (pad_to(cfg.intermediate_size, MATRIX_ROW_PADDING) / 32) * 36;
-    ws.y_a = take(ws.y_a_bytes); ws.y_b = take(ws.y_b_bytes);
-    const size_t parts = (size_t)mrs_decode_attention_max_splits(cfg.max_context_len);
-    ws.attn_ws = take(B * cfg.num_heads * parts * cfg.head_dim * 4);
-    ws.exp_sums = (float *)take(B * cfg.num_heads * parts * 4);
-    ws.max_logits = (float *)take(B * cfg.num_heads * parts * 4);
-    ws.sample_scratch = take(B * 8);
-    ws.attn_img = take(mrs_dec_act_image_bytes((int)nq, (int)B));
-    ws.attn_ticket = (unsigned *)take(B * (size_t)cfg.num_kv_heads * 4);
-    ws.act_img = take(mrs_dec_act_image_bytes(std::max((int)d, (int)cfg.intermediate_size), (int)std::min<size_t>(B, 8)));
-    if (cfg.num_experts > 0) {
-      const size_t k = std::max(1, (int)cfg.num_experts_per_tok);
-      ws.moe_ids = (int32_t *)take(B * k * 4); ws.moe_w = (float *)take(B * k * 4);
-      ws.moe_y = take(k * (pad_to(cfg.intermediate_size, MATRIX_ROW_PADDING) / 32) * 36);
-      ws.moe_act = (float *)take(k * (size_t)cfg.intermediate_size * 4);
-      ws.moe_router_scratch = take(mrs_moe_router_split_scratch_bytes((int)B, (int)cfg.num_experts));
-    }
+    lay_out(cfg, b.workspace, ws);
     // zero once: Q8_1 padding blocks beyond K are never written by the fused epilogues; sample scratch must start at 0
     if (hipMemset(b.workspace, 0, b.workspace_bytes) != hipSuccess) return fail("hipMemset(workspace) failed");
     have_bufs = true;
@@ -304,16 +305,21 @@ class Llama {
     return true;
   }
 
+  // what every attention launch (decode and prompt) takes from the config
+  struct AttnGeom { int eff_max; float scale; int block_stride, head_stride, kvd; };  // longest context of a block table; 1 / sqrt(head_dim); elements per page / per KV head of a page; engine page dtype (1 bf16, 0 f16)
+  AttnGeom attn_geom() const {
+    const int hd = cfg.head_dim, bs = cfg.block_size;
+    return AttnGeom{std::min(cfg.max_blocks_per_seq * bs, cfg.max_context_len), 1.0f / sqrtf((float)hd), cfg.num_kv_heads * hd * bs, hd * bs, cfg.kv_f16 ? 0 : 1};
+  }
+
   // PagedAttention::forward, decode branch (run_decode): attention over the cache that already holds this token
   int paged_attention_decode(const Block &bl, int b, hipStream_t s) const {
-    const int hd = cfg.head_dim, bs = cfg.block_size, kvh = cfg.num_kv_heads;
-    const int kv_block_stride = kvh * hd * bs, kv_head_stride = hd * bs;
-    const int eff_max = std::min(cfg.max_blocks_per_seq * bs, cfg.max_context_len);
-    const int parts = (eff_max + 511) / 512;
+    const AttnGeom ag = attn_geom();
+    const int parts = (ag.eff_max + 511) / 512;
     const bool use_v1 = (parts == 1 || b * cfg.num_heads > 512);  // paged_attention.rs:302-307
     mrs_paged_attention_f32_bf16(use_v1 ? 0 : 1, ws.attn, ws.exp_sums, ws.max_logits, ws.attn_ws, ws.q, bl.key_cache, bl.value_cache,
-                                 nullptr, kvh, 1.0f / sqrtf((float)hd), 1.0f, bufs.block_tables, bufs.context_lens, bs, eff_max, b,
-                                 cfg.num_heads, hd, cfg.max_blocks_per_seq, cfg.num_heads * hd, kv_block_stride, kv_head_stride, s, nullptr);
+                                 nullptr, cfg.num_kv_heads, ag.scale, 1.0f, bufs.block_tables, bufs.context_lens, cfg.block_size, ag.eff_max, b,
+                                 cfg.num_heads, cfg.head_dim, cfg.max_blocks_per_seq, cfg.num_heads * cfg.head_dim, ag.block_stride, ag.head_stride, s, nullptr);
     return 0;
   }
 
@@ -358,6 +364,8 @@ class Llama {
     const float rs = 1.0f / (float)std::max(1, (int)cfg.world_size);
     const int d = cfg.hidden_size, hd = cfg.head_dim, nq = cfg.num_heads * hd, nkv = cfg.num_kv_heads * hd, ff = cfg.intermediate_size;
     const int stride_q = pad_to(nq, MATRIX_ROW_PADDING) / 32, stride_f = pad_to(ff, MATRIX_ROW_PADDING) / 32;
+    const int bs = cfg.block_size, kvh = cfg.num_kv_heads;
+    const AttnGeom ag = attn_geom();
     if (wte->embedding_forward_raw(bufs.input_ids, b, ws.h, s)) return -1;
     for (const Block &bl : blocks) {
       const QTensor *q = bl.q_proj->get_qtensor(), *k = bl.k_proj->get_qtensor(), *v = bl.v_proj->get_qtensor();
@@ -365,11 +373,9 @@ class Llama {
                          cfg.rms_eps, ws.q, bl.key_cache, bl.value_cache, bufs.slot_mapping, bufs.positions, bufs.cos_table,
                          bufs.sin_table, hd, cfg.rot_dim / 2, cfg.num_kv_heads, cfg.block_size, b, s))
         return fail("mrs_decode_qkv refused the layer");
-      const int bs = cfg.block_size, kvh = cfg.num_kv_heads;
-      const int eff_max = std::min(cfg.max_blocks_per_seq * bs, cfg.max_context_len);
       if (mrs_decode_attention_q8_1_f32_bf16(ws.y_a, stride_q, ws.exp_sums, ws.max_logits, ws.attn_ws, ws.q, bl.key_cache, bl.value_cache, kvh,
-                                             1.0f / sqrtf((float)hd), bufs.block_tables, bufs.context_lens, bs, eff_max, b, cfg.num_heads, hd,
-                                             cfg.max_blocks_per_seq, cfg.num_heads * hd, kvh * hd * bs, hd * bs, s)) {
+                                             ag.scale, bufs.block_tables, bufs.context_lens, bs, ag.eff_max, b, cfg.num_heads, hd,
+                                             cfg.max_blocks_per_seq, cfg.num_heads * hd, ag.block_stride, ag.head_stride, s)) {
         paged_attention_decode(bl, b, s);  // shapes outside the split kernel: reference-partitioned attention + quantize
         mrs_quantize_rows_q8_1(ws.attn, ws.y_a, nq, stride_q, b, s);
       }
@@ -501,9 +507,9 @@ class Llama {
   // changed the state) and lm_head folds the arg-max into its epilogue: the captured step is two launches shorter (no embedding_kernel, no argmax_partial_kernel)
   int forward_engine(int b, hipStream_t s, bool chained = false) const {
     const float rs = 1.0f / (float)std::max(1, (int)cfg.world_size);
-    const int d = cfg.hidden_size, hd = cfg.head_dim, nq = cfg.num_heads * hd, ff = cfg.intermediate_size, kvd = cfg.kv_f16 ? 0 : 1;
+    const int d = cfg.hidden_size, hd = cfg.head_dim, nq = cfg.num_heads * hd, ff = cfg.intermediate_size;
     const int bs = cfg.block_size, kvh = cfg.num_kv_heads;
-    const int eff_max = std::min(cfg.max_blocks_per_seq * bs, cfg.max_context_len);
+    const AttnGeom ag = attn_geom();
     if (chained && b != 1) return fail("chained decode step: batch 1 only");
     if (!chained && wte->embedding_forward_raw(bufs.input_ids, b, ws.h, s)) return -1;
     for (const Block &bl : blocks) {
@@ -511,8 +517,8 @@ class Llama {
       // one launch: splits + last-arriver merge; even GQA groups hand o_proj the Q8_K image of the result (Q8_0 weights take Q8_0 activations: f32 result)
       const bool want_img = bl.dout.type != 8 && (cfg.num_heads / kvh) % 2 == 0 && mrs_dec_act_image_bytes(nq, b) <= mrs_dec_proj_img_max_bytes();
       const int rc2 = mrs_dec_attention(want_img ? nullptr : ws.attn, want_img ? ws.attn_img : nullptr, ws.attn_ticket, (float *)ws.attn_ws, ws.max_logits, ws.exp_sums, ws.q,
-                                        bl.key_cache, bl.value_cache, kvh, 1.0f / sqrtf((float)hd), bufs.block_tables, bufs.context_lens, bs, eff_max, b, cfg.num_heads, hd,
-                                        cfg.max_blocks_per_seq, nq, kvh * hd * bs, hd * bs, kvd, cfg.sliding_window, s);
+                                        bl.key_cache, bl.value_cache, kvh, ag.scale, bufs.block_tables, bufs.context_lens, bs, ag.eff_max, b, cfg.num_heads, hd,
+                                        cfg.max_blocks_per_seq, nq, ag.block_stride, ag.head_stride, ag.kvd, cfg.sliding_window, s);
       if (rc2 < 0) return fail("mrs_dec_attention refused the shape");
       // TP: h <- h / world + W_o . attn on every rank, then ONE sum all-reduce of h (the residual add stays fused, as in forward_fused).  An f32 attention result (odd GQA
       // groups, Q8_0 o_proj) is quantized inside the GEMV at every batch size.
@@ -561,40 +567,105 @@ class Llama {
     return 0;
   }
 
-  // ---- prefill: T prompt tokens of one sequence through the bf16-MFMA GEMMs (role of fast_mmq::* + the prompt branch
-  //      of PagedAttention::forward).  Buffers are carved from the caller's prefill workspace.
+  // ---- prefill: T prompt tokens of one sequence (role of fast_mmq::* + the prompt branch of PagedAttention::forward): prefill() at the end of this section lays the caller's
+  //      prefill workspace out as one PrefillBufs and picks one of the three paths listed in the header of this file
   // prompts longer than this use the 256-row-tile GEMM over bf16 slabs (its L1-bypassing A loads beat the 128-row f32 kernel even when
   // half of the tile rows are empty: TTFT 16.3 -> 10.1 ms at T = 128, 19.5 -> 8.3 ms at T = 64, 18.5 -> 7.7 ms at T = 32)
   static constexpr int prefill_big_min = 16;
-  static size_t prefill_workspace_bytes(const mrs_llama_config &c, int T) {
-    const size_t t = (size_t)T, d = c.hidden_size, nq = (size_t)c.num_heads * c.head_dim, nkv = (size_t)c.num_kv_heads * c.head_dim;
-    const size_t ff = c.intermediate_size;
-    size_t b = 0;
-    b += align(t * d * 4) * 2;        // h, xn
-    b += align(t * nq * 4) * 2;       // q, attn
-    b += align(t * nkv * 4) * 2;      // k, v
-    b += align(t * ff * 4) * 3;       // gate, up, act
-    b += align((pad_to((int)d, MATRIX_ROW_PADDING) / 32) * 36);  // Q8_1 scratch of the last-token lm_head GEMV
-    b += align(mrs_qi_act_bytes(T, (int)std::max(std::max(d, nq), ff))) + align(mrs_gemm_qi_workspace_bytes(T, (int)std::max(d, nq)));  // exact prompt path: Q8_K operands of T rows (f16 quants, scales, run sums) + run sums of split launches
-    if (T > prefill_big_min) b += align(t * std::max(std::max(d, nq), ff) * 2) + align(mrs_gemm_q_bf16_workspace_bytes(T));  // bf16 activations + split-K partials
-    if (c.num_experts > 0) {  // MoE FFN of the prompt: routes = T * top_k rows in expert-sorted order
+  // Every buffer of the three prompt paths.  The layout depends on (cfg, T) alone, never on the prefill mode: buffers with the same role are one member that the paths
+  // share, a buffer only one path uses has its own place next to them, and the size the caller is asked for is where this layout ends.
+  struct PrefillBufs {
+    float *h, *xn, *q, *attn, *k, *v;
+    float *g, *u, *act;                  // dense FFN, [T][ff] each (the shadow path also parks its one-GEMM q / k / v in g, free until the FFN)
+    void *lm_q8; size_t lm_q8_bytes;     // dequant path: Q8_1 row of the last-token lm_head GEMV when mrs_decode_norm_proj does not take lm_head's dtype
+    void *qact, *qws; size_t qws_bytes;  // exact path: Q8_K / Q8_0 operands of T rows (f16 quants, scales, run sums) + run sums of split launches
+    void *xb, *part; size_t part_bytes;  // T > prefill_big_min, shadow + dequant paths: bf16 activations (rows / slabs) of the widest linear + split-K partials
+    // sparse MoE (cfg.num_experts > 0): routes = T * top_k rows in expert-sorted order
+    float *rg, *ru, *ract;               // gate, up, act per route, [routes][ff] (the FFN of a MoE block uses these, not g / u / act)
+    int32_t *ids, *sorted, *bounds, *counts, *cursors;  // expert ids, sorted routes; per expert: bounds [E + 1], counts, cursors
+    float *w;                            // routing weights
+    void *y_in, *y_act; float *sum;      // dequant path: Q8_1 rows of the normed hidden states / of the routes' activations; sum of the weighted expert outputs
+    void *moe_xb, *moe_yb;               // dequant path, T > prefill_big_min: bf16 slabs of the normed tokens / of the routes' activations (matrix-core route)
+    int32_t *inv; float *y; void *qact_g, *qact_r;  // exact path: inverse route table, per-route down outputs, gathered / per-route operand rows
+    // The shadow path's one-GEMM gate / up writes [T][2 ff] across g and u.  They are two consecutive takes, so u starts where g ends exactly when T * ff * 4 is a multiple of
+    // the arena's 256-byte alignment; otherwise the path makes two GEMMs.
+    bool gate_up_adjacent(int T, int ff) const { return u == g + (size_t)T * ff; }
+  };
+  static size_t lay_out_prefill(const mrs_llama_config &c, int T, void *base, PrefillBufs &P) {
+    const size_t t = (size_t)T, d = c.hidden_size, nq = (size_t)c.num_heads * c.head_dim, nkv = (size_t)c.num_kv_heads * c.head_dim, ff = c.intermediate_size;
+    const size_t widest = std::max(std::max(d, nq), ff);
+    const bool big = T > prefill_big_min;
+    Arena a(base);
+    P = PrefillBufs{};
+    P.h = a.take<float>(t * d * 4); P.xn = a.take<float>(t * d * 4);
+    P.q = a.take<float>(t * nq * 4); P.attn = a.take<float>(t * nq * 4);
+    P.k = a.take<float>(t * nkv * 4); P.v = a.take<float>(t * nkv * 4);
+    P.g = a.take<float>(t * ff * 4); P.u = a.take<float>(t * ff * 4); P.act = a.take<float>(t * ff * 4);
+    P.lm_q8_bytes = (size_t)(pad_to((int)d, MATRIX_ROW_PADDING) / 32) * 36; P.lm_q8 = a.take(P.lm_q8_bytes);
+    P.qact = a.take(mrs_qi_act_bytes(T, (int)widest));
+    P.qws_bytes = mrs_gemm_qi_workspace_bytes(T, (int)std::max(d, nq)); P.qws = a.take(P.qws_bytes);
+    if (big) { P.xb = a.take(t * widest * 2); P.part_bytes = mrs_gemm_q_bf16_workspace_bytes(T); P.part = a.take(P.part_bytes); }
+    if (c.num_experts > 0) {
       const size_t tk = (size_t)std::max(1, (int)c.num_experts_per_tok), r = t * tk, E = (size_t)c.num_experts;
-      b += align(r * ff * 4) * 3;                                                    // gate, up, act per route (replace the dense t * ff buffers)
-      b += align(r * 4) * 3 + align((E + 1) * 4) + align(E * 4) * 2;                  // ids, weights, sorted routes; bounds, counts, cursors
-      b += align(t * (pad_to((int)d, MATRIX_ROW_PADDING) / 32) * 36);                // Q8_1 rows of the normed hidden states
-      b += align(r * (pad_to((int)ff, MATRIX_ROW_PADDING) / 32) * 36);               // Q8_1 rows of the routes' activations
-      b += align(t * d * 4);                                                         // sum of the weighted expert outputs
-      if (T > prefill_big_min) b += align(t * d * 2) + align(r * ff * 2);         // bf16 slabs of the normed tokens and of the routes' activations
-      b += align(r * 4) + align(r * d * 4) + align(mrs_qi_act_bytes((int)r, (int)d)) + align(mrs_qi_act_bytes((int)r, (int)ff));  // exact path: inverse route table, per-route down outputs, gathered / per-route operand rows
+      P.rg = a.take<float>(r * ff * 4); P.ru = a.take<float>(r * ff * 4); P.ract = a.take<float>(r * ff * 4);
+      P.ids = a.take<int32_t>(r * 4); P.w = a.take<float>(r * 4); P.sorted = a.take<int32_t>(r * 4);
+      P.bounds = a.take<int32_t>((E + 1) * 4); P.counts = a.take<int32_t>(E * 4); P.cursors = a.take<int32_t>(E * 4);
+      P.y_in = a.take(t * (pad_to((int)d, MATRIX_ROW_PADDING) / 32) * 36);
+      P.y_act = a.take(r * (pad_to((int)ff, MATRIX_ROW_PADDING) / 32) * 36);
+      P.sum = a.take<float>(t * d * 4);
+      if (big) { P.moe_xb = a.take(t * d * 2); P.moe_yb = a.take(r * ff * 2); }
+      P.inv = a.take<int32_t>(r * 4); P.y = a.take<float>(r * d * 4);
+      P.qact_g = a.take(mrs_qi_act_bytes((int)r, (int)d)); P.qact_r = a.take(mrs_qi_act_bytes((int)r, (int)ff));
     }
-    return b + 4096;
+    return a.off;
   }
+  static size_t prefill_workspace_bytes(const mrs_llama_config &c, int T) { PrefillBufs P; return lay_out_prefill(c, T, nullptr, P) + WORKSPACE_SLACK; }
+
+  // ---- layer steps the prompt paths share
+  // rotary on q / k rows of the given strides, then k / v into the layer's pages (cache_kind: reshape_and_cache's page dtype selector)
+  void rope_and_cache(const Block &bl, float *q, float *k, float *v, int q_stride, int kv_stride, int cache_kind, const mrs_llama_prefill_args &pa, int T, hipStream_t s) const {
+    rotary_embedding_positions(q, k, (void *)bufs.cos_table, (void *)bufs.sin_table, (void *)pa.positions, cfg.rope_interleaved ? 0 : 1, cfg.head_dim, T,
+                               cfg.rot_dim / 2, cfg.max_context_len, cfg.num_heads, cfg.num_kv_heads, q_stride, kv_stride, 2, (int64_t)(intptr_t)s);
+    reshape_and_cache(k, v, bl.key_cache, bl.value_cache, (int64_t *)pa.slot_mapping, T, cfg.num_kv_heads, cfg.head_dim, cfg.block_size, 8, kv_stride, kv_stride, s, 2, cache_kind,
+                      nullptr, nullptr);
+  }
+  // o_proj / down_proj of the bf16 paths, gemm(out, accumulate): h += W . x; row-parallel shards: partial into xn -> all-reduce -> residual add (bias-free)
+  template <class Gemm> int residual_gemm(Gemm &&gemm, const PrefillBufs &P, int T, hipStream_t s) const {
+    const size_t n = (size_t)T * cfg.hidden_size;
+    if (cfg.world_size > 1) return (gemm(P.xn, 0) || all_reduce(P.xn, n, s) || mrs_vec_add_f32(P.h, P.xn, n, s)) ? -1 : 0;
+    return gemm(P.h, 1) ? -1 : 0;
+  }
+  // Projections that share their input run per weight format: for every key(dtype) in first-appearance order, body(the projections with that key, in list order)
+  struct Proj { const GgufMatMul *m; int n; float *out; int dtype() const { return m->get_qtensor()->dtype; } };
+  template <class Key, class Body> static int by_format(std::initializer_list<Proj> ps, Key key, Body body) {
+    const Proj *p = ps.begin();
+    std::vector<bool> done(ps.size(), false);
+    std::vector<Proj> grp;
+    for (size_t i = 0; i < ps.size(); ++i) {
+      if (done[i]) continue;
+      grp.clear();
+      for (size_t j = i; j < ps.size(); ++j)
+        if (!done[j] && key(p[j].dtype()) == key(p[i].dtype())) { grp.push_back(p[j]); done[j] = true; }
+      if (body(grp)) return -1;
+    }
+    return 0;
+  }
+  // ctx.logits: only the last prompt token reaches lm_head (llama.rs:514-517): final norm + lm_head in one launch; dtypes outside that kernel: norm, then the reference's GEMV
+  int last_token_logits(const PrefillBufs &P, const mrs_llama_prefill_args &pa, int T, hipStream_t s) const {
+    const QTensor *lm = lm_head->get_qtensor();
+    const int d = cfg.hidden_size;
+    const float *last = P.h + (size_t)(T - 1) * d;
+    if (mrs_decode_gemv_supported(lm->dtype))
+      return mrs_decode_norm_proj(lm->data, lm->dtype, cfg.vocab_size, d, last, ln_f, cfg.rms_eps, pa.logits, cfg.vocab_size, 1, s) ? fail("prefill: lm_head refused") : 0;
+    mrs_rms_norm_f32(last, ln_f, P.xn, 1, d, cfg.rms_eps, (int64_t)(intptr_t)s);
+    return lm_head->forward_raw(P.xn, 1, pa.logits, Scratch{P.lm_q8, P.lm_q8_bytes}, s);
+  }
+
   // MoE FFN of a prompt (SparseMoeBlock::forward on [T, hidden], models/mixtral.rs:280-304; the reference's prompt route is
   // FastExpertsWeights::forward_* -> moe_dispatch_build + grouped GEMM, moe/experts/backends.rs:969-1100, gguf/cuda.rs:590-640,1340-1420):
   // router top-k on the device, stable dispatch by expert, grouped gate / up GEMMs over the expert-sorted routes (every expert's weights are
   // read once per 8 of ITS routes instead of once per token), SiLU * up, grouped down GEMM that scales by the routing weight and sums the
   // top-k routes of a token with f32 atomics into a zeroed buffer (top-k = 2: order-independent), residual add.  No host sync.
-  struct MoePrefillBufs { int32_t *ids, *sorted, *bounds, *counts, *cursors; float *w, *g, *u, *act, *sum; void *y_in, *y_act; void *xb, *yb; };  // xb / yb: bf16 slabs of the normed tokens / of the routes' activations (matrix-core route)
   typedef void (*moe_grouped_fn)(const void *, const void *, const int32_t *, const int32_t *, const float *, float *, int, int, int, int, int, int, void *);
   static moe_grouped_fn grouped_gemm_for(int dtype) {
     const DTypeInfo *ti = type_info(dtype);
@@ -604,9 +675,10 @@ class Llama {
     if (us != std::string::npos) tag.erase(us, 1);
     return (moe_grouped_fn)lookup("launch_moe_grouped_gemm_" + tag);
   }
-  int moe_ffn_prefill(const Block &bl, float *h, float *xn, int T, const MoePrefillBufs &m, hipStream_t s) const {
+  int moe_ffn_prefill(const Block &bl, const PrefillBufs &m, int T, hipStream_t s) const {
     const int d = cfg.hidden_size, ff = cfg.intermediate_size, E = cfg.num_experts, tk = cfg.num_experts_per_tok, routes = T * tk;
     const int kp_d = pad_to(d, MATRIX_ROW_PADDING), kp_ff = pad_to(ff, MATRIX_ROW_PADDING);
+    float *h = m.h, *xn = m.xn;
     const moe_grouped_fn gate_up = grouped_gemm_for(bl.gate_exps.dtype), down = grouped_gemm_for(bl.down_exps.dtype);
     if (!gate_up || !down || bl.up_exps.dtype != bl.gate_exps.dtype) return fail("prefill: no grouped MoE GEMM for expert dtypes %d / %d / %d", bl.gate_exps.dtype, bl.up_exps.dtype, bl.down_exps.dtype);
     mrs_rms_norm_f32(h, bl.post_attention_layernorm, xn, T, d, cfg.rms_eps, (int64_t)(intptr_t)s);
@@ -614,22 +686,22 @@ class Llama {
     launch_moe_dispatch(m.ids, m.bounds, m.sorted, nullptr, routes, E, tk, m.counts, m.cursors, s);
     // long prompts: the grouped GEMMs on the matrix cores (block dequant -> bf16 MFMA, the dense prompt GEMM's arithmetic) over the same dispatch
     // tables -- every expert's weights are decoded once per 256 of ITS routes.  Short prompts and other shapes take the int8-dot grouped GEMV route below.
-    if (m.xb && m.yb && d % 64 == 0 && ff % 64 == 0 && bl.up_exps.dtype == bl.gate_exps.dtype) {
-      int rc = mrs_convert_f32_bf16_slabs(xn, d, T, d, m.xb, s);
-      if (!rc) rc = mrs_moe_gemm_q_bf16(bl.gate_exps.data, bl.gate_exps.dtype, ff, d, E, m.xb, T, m.bounds, m.sorted, tk, 1, nullptr, m.g, ff, routes, s);
-      if (!rc) rc = mrs_moe_gemm_q_bf16(bl.up_exps.data, bl.up_exps.dtype, ff, d, E, m.xb, T, m.bounds, m.sorted, tk, 1, nullptr, m.u, ff, routes, s);
-      if (!rc) rc = mrs_glu_bf16_slabs(m.g, m.u, ff, routes, ff, 0, m.yb, s);
+    if (m.moe_xb && m.moe_yb && d % 64 == 0 && ff % 64 == 0 && bl.up_exps.dtype == bl.gate_exps.dtype) {
+      int rc = mrs_convert_f32_bf16_slabs(xn, d, T, d, m.moe_xb, s);
+      if (!rc) rc = mrs_moe_gemm_q_bf16(bl.gate_exps.data, bl.gate_exps.dtype, ff, d, E, m.moe_xb, T, m.bounds, m.sorted, tk, 1, nullptr, m.rg, ff, routes, s);
+      if (!rc) rc = mrs_moe_gemm_q_bf16(bl.up_exps.data, bl.up_exps.dtype, ff, d, E, m.moe_xb, T, m.bounds, m.sorted, tk, 1, nullptr, m.ru, ff, routes, s);
+      if (!rc) rc = mrs_glu_bf16_slabs(m.rg, m.ru, ff, routes, ff, 0, m.moe_yb, s);
       if (!rc && hipMemsetAsync(m.sum, 0, (size_t)T * d * 4, s) != hipSuccess) return fail("prefill: hipMemsetAsync failed");
-      if (!rc) rc = mrs_moe_gemm_q_bf16(bl.down_exps.data, bl.down_exps.dtype, d, ff, E, m.yb, routes, m.bounds, m.sorted, tk, 0, m.w, m.sum, d, routes, s);
+      if (!rc) rc = mrs_moe_gemm_q_bf16(bl.down_exps.data, bl.down_exps.dtype, d, ff, E, m.moe_yb, routes, m.bounds, m.sorted, tk, 0, m.w, m.sum, d, routes, s);
       if (!rc && all_reduce(m.sum, (size_t)T * d, s)) return fail("prefill: moe all-reduce failed: %s", g_last_error.c_str());  // TP: experts sharded on ffn
       if (!rc) return mrs_vec_add_f32(h, m.sum, (size_t)T * d, s) ? fail("prefill: residual add failed") : 0;
       if (rc != -1) return fail("prefill: grouped MoE GEMM on the matrix cores failed (%d)", rc);  // -1: a dtype outside that kernel -> the route below
     }
     launch_mmvq_gguf_quantize_q8_1_f32(xn, m.y_in, d, kp_d, T, s);
-    gate_up(bl.gate_exps.data, m.y_in, m.bounds, m.sorted, nullptr, m.g, ff, d, kp_d, E, tk, 1, s);  // input_dim1 = 1: the token's row; out[sorted position]
-    gate_up(bl.up_exps.data, m.y_in, m.bounds, m.sorted, nullptr, m.u, ff, d, kp_d, E, tk, 1, s);
-    fused_glu_f32(m.g, m.u, m.act, (uint32_t)routes, (uint32_t)ff, (uint32_t)ff, (uint32_t)ff, 0, s);
-    launch_mmvq_gguf_quantize_q8_1_f32(m.act, m.y_act, ff, kp_ff, routes, s);
+    gate_up(bl.gate_exps.data, m.y_in, m.bounds, m.sorted, nullptr, m.rg, ff, d, kp_d, E, tk, 1, s);  // input_dim1 = 1: the token's row; out[sorted position]
+    gate_up(bl.up_exps.data, m.y_in, m.bounds, m.sorted, nullptr, m.ru, ff, d, kp_d, E, tk, 1, s);
+    fused_glu_f32(m.rg, m.ru, m.ract, (uint32_t)routes, (uint32_t)ff, (uint32_t)ff, (uint32_t)ff, 0, s);
+    launch_mmvq_gguf_quantize_q8_1_f32(m.ract, m.y_act, ff, kp_ff, routes, s);
     if (hipMemsetAsync(m.sum, 0, (size_t)T * d * 4, s) != hipSuccess) return fail("prefill: hipMemsetAsync failed");
     down(bl.down_exps.data, m.y_act, m.bounds, m.sorted, m.w, m.sum, d, ff, kp_ff, E, tk, 0, s);     // input_dim1 = 0: rows already in sorted order
     if (all_reduce(m.sum, (size_t)T * d, s)) return fail("prefill: moe all-reduce failed: %s", g_last_error.c_str());
@@ -642,11 +714,9 @@ class Llama {
   int prefill_mode = -1;  // -1: MRS_PREFILL_EXACT (default 1); 0: bf16-operand MFMA prompt GEMMs (library GEMMs on the bf16 shadow copy when every dense linear has one, else mrs_gemm_q_bf16_multi; + flash attention); 1: exact path; 2: as 0 with the fused-dequant kernels forced
   bool bf16_shadow_ok() const {
     if (cfg.num_experts > 0 || blocks.empty()) return false;
-    for (const Block &bl : blocks) {
-      const GgufMatMul *ls[7] = {bl.q_proj.get(), bl.k_proj.get(), bl.v_proj.get(), bl.o_proj.get(), bl.gate_proj.get(), bl.up_proj.get(), bl.down_proj.get()};
-      for (const GgufMatMul *l : ls)
+    for (const Block &bl : blocks)
+      for (const GgufMatMul *l : bl.dense())
         if (!l || !l->get_qtensor() || !l->get_qtensor()->bf16) return false;
-    }
     return true;
   }
   bool prefill_exact_ok() const {
@@ -659,142 +729,157 @@ class Llama {
     if (cfg.num_heads % cfg.num_kv_heads || (G != 1 && G != 2 && G != 4 && G != 8)) return false;
     const bool moe = cfg.num_experts > 0;
     for (const Block &bl : blocks) {
-      const GgufMatMul *ls[7] = {bl.q_proj.get(), bl.k_proj.get(), bl.v_proj.get(), bl.o_proj.get(), bl.gate_proj.get(), bl.up_proj.get(), bl.down_proj.get()};
+      const auto ls = bl.dense();
       for (int i = 0; i < (moe ? 4 : 7); ++i)
         if (!ls[i] || !ls[i]->get_qtensor() || !ls[i]->get_qtensor()->qi) return false;
       if (moe && (!bl.gate_exps.qi || !bl.up_exps.qi || !bl.down_exps.qi || !bl.router || bl.gate_exps.dtype != bl.up_exps.dtype || cfg.intermediate_size % 32 || cfg.hidden_size % 32)) return false;
     }
     return dlm_head.planes != nullptr;
   }
-  struct MoeExactBufs { int32_t *ids, *sorted, *inv, *bounds, *counts, *cursors; float *w, *y; void *qact_g, *qact_r; };  // routes = T * top_k rows in expert-sorted order
   // SparseMoeBlock::forward of a prompt in the decode step's arithmetic: the step's router kernel on every token, the tokens' Q8_K / Q8_0 rows gathered into
   // expert-sorted order, every expert's gate / up / down as one window of the exact GEMM, silu(g) * u quantized per route, the slots folded into h in slot order
-  int moe_ffn_exact(const Block &bl, int T, float *h, float *g, float *u, float *act, void *qact, const MoeExactBufs &m, hipStream_t s) const {
+  int moe_ffn_exact(const Block &bl, const PrefillBufs &m, int T, hipStream_t s) const {
     const int d = cfg.hidden_size, ff = cfg.intermediate_size, E = cfg.num_experts, tk = cfg.num_experts_per_tok, R = T * tk;
     const float rs = 1.0f / (float)std::max(1, (int)cfg.world_size);
+    float *h = m.h;
     const int rrc = mrs_moe_router_topk_norm(h, bl.post_attention_layernorm, cfg.rms_eps, bl.router, T, E, d, tk, 1, m.ids, m.w, s);
     if (rrc) return fail("prefill (exact): moe router refused (%d)", rrc);  // (-3, rows beyond 64 KiB, takes the two-launch router in the decode step: not a shape of this path)
     launch_moe_dispatch(m.ids, m.bounds, m.sorted, nullptr, R, E, tk, m.counts, m.cursors, s);
     const int tg = bl.gate_exps.dtype, td = bl.down_exps.dtype;
-    if (mrs_qi_quantize_for(tg, h, nullptr, d, bl.post_attention_layernorm, cfg.rms_eps, T, d, qact, nullptr, s)) return fail("prefill (exact): activation quantizer refused K=%d", d);
-    if (mrs_qi_gather_rows(tg, qact, T, m.qact_g, R, d, m.sorted, tk, m.inv, s)) return fail("prefill (exact): operand gather refused");
+    if (mrs_qi_quantize_for(tg, h, nullptr, d, bl.post_attention_layernorm, cfg.rms_eps, T, d, m.qact, nullptr, s)) return fail("prefill (exact): activation quantizer refused K=%d", d);
+    if (mrs_qi_gather_rows(tg, m.qact, T, m.qact_g, R, d, m.sorted, tk, m.inv, s)) return fail("prefill (exact): operand gather refused");
     const size_t pg = mrs_gemm_qi_repack_bytes(tg, ff, d), pd = mrs_gemm_qi_repack_bytes(td, d, ff);  // bytes of one expert's panels
     for (int e = 0; e < E; ++e) {
-      if (mrs_gemm_qi_win((const char *)bl.gate_exps.qi + (size_t)e * pg, tg, ff, d, m.qact_g, R, m.bounds + e, T, g, ff, 0, s) ||
-          mrs_gemm_qi_win((const char *)bl.up_exps.qi + (size_t)e * pg, tg, ff, d, m.qact_g, R, m.bounds + e, T, u, ff, 0, s))
+      if (mrs_gemm_qi_win((const char *)bl.gate_exps.qi + (size_t)e * pg, tg, ff, d, m.qact_g, R, m.bounds + e, T, m.rg, ff, 0, s) ||
+          mrs_gemm_qi_win((const char *)bl.up_exps.qi + (size_t)e * pg, tg, ff, d, m.qact_g, R, m.bounds + e, T, m.ru, ff, 0, s))
         return fail("prefill (exact): expert gate / up GEMM refused (ggml dtype %d)", tg);
     }
-    if (mrs_qi_quantize_for(td, g, u, ff, nullptr, 0.f, R, ff, m.qact_r, act, s)) return fail("prefill (exact): activation quantizer refused K=%d", ff);
+    if (mrs_qi_quantize_for(td, m.rg, m.ru, ff, nullptr, 0.f, R, ff, m.qact_r, m.ract, s)) return fail("prefill (exact): activation quantizer refused K=%d", ff);
     for (int e = 0; e < E; ++e)
       if (mrs_gemm_qi_win((const char *)bl.down_exps.qi + (size_t)e * pd, td, d, ff, m.qact_r, R, m.bounds + e, T, m.y, d, 0, s)) return fail("prefill (exact): expert down GEMM refused (ggml dtype %d)", td);
     if (mrs_moe_fold_exact(h, rs, m.y, m.inv, m.w, T, d, tk, s)) return fail("prefill (exact): moe fold refused");
     return all_reduce(h, (size_t)T * d, s) ? fail("prefill (exact): moe all-reduce failed: %s", g_last_error.c_str()) : 0;
   }
-  int prefill_exact(const mrs_llama_prefill_args &pa, int T, float *h, float *xn, float *q, float *k, float *v, float *attn, float *g, float *u, float *act, void *qact,
-                    void *qws, size_t qws_bytes, const MoeExactBufs &mx, hipStream_t s) const {
+  int prefill_exact(const PrefillBufs &P, const mrs_llama_prefill_args &pa, int T, hipStream_t s) const {
     const int d = cfg.hidden_size, hd = cfg.head_dim, nq = cfg.num_heads * hd, nkv = cfg.num_kv_heads * hd, ff = cfg.intermediate_size;
-    const int bs = cfg.block_size, kvh = cfg.num_kv_heads, kvd = cfg.kv_f16 ? 0 : 1;
-    const int eff_max = std::min(cfg.max_blocks_per_seq * bs, cfg.max_context_len);
-    const int64_t st = (int64_t)(intptr_t)s;
+    const AttnGeom ag = attn_geom();
+    float *h = P.h;
     auto lin = [&](const GgufMatMul &m, int N, int K, float *out, int acc) -> int {
       const QTensor *w = m.get_qtensor();
-      return mrs_gemm_qi_ws(w->qi, w->dtype, N, K, qact, T, out, N, acc, N <= std::max(d, nq) ? qws : nullptr, qws_bytes, s) ? fail("prefill (exact): mrs_gemm_qi refused ggml dtype %d (N=%d K=%d)", w->dtype, N, K) : 0;
+      return mrs_gemm_qi_ws(w->qi, w->dtype, N, K, P.qact, T, out, N, acc, N <= std::max(d, nq) ? P.qws : nullptr, P.qws_bytes, s) ? fail("prefill (exact): mrs_gemm_qi refused ggml dtype %d (N=%d K=%d)", w->dtype, N, K) : 0;
     };
     // o_proj / down_proj: h <- h + W . x;  tensor parallel: h <- h * (1 / world) + W_shard . x on every rank (the decode step's RESID epilogue, two roundings), then ONE
     // sum all-reduce of h (distributed/layers.rs:965-975) -- the same sums as the decode step whenever the all-reduce adds the ranks in the same order (world 2: always;
-    // the peer-mailbox route: rank order for every message it takes)
+    // the peer-mailbox route: rank order for every message it takes).  Not residual_gemm: the scaled add comes BEFORE the all-reduce here.
     const float rs = 1.0f / (float)std::max(1, (int)cfg.world_size);
     auto row_parallel = [&](const GgufMatMul &m, int N, int K, const float *x, const float *x2, int ldx, float *xtmp) -> int {
       const int ty = m.get_qtensor()->dtype;
-      if (mrs_qi_quantize_for(ty, x, x2, ldx, nullptr, 0.f, T, K, qact, xtmp, s)) return fail("prefill (exact): activation quantizer refused K=%d (ggml dtype %d)", K, ty);
+      if (mrs_qi_quantize_for(ty, x, x2, ldx, nullptr, 0.f, T, K, P.qact, xtmp, s)) return fail("prefill (exact): activation quantizer refused K=%d (ggml dtype %d)", K, ty);
       if (cfg.world_size <= 1) return lin(m, N, K, h, 1);
-      if (lin(m, N, K, xn, 0) || mrs_resid_scale_add_f32(h, rs, xn, (size_t)T * N, s)) return -1;
+      if (lin(m, N, K, P.xn, 0) || mrs_resid_scale_add_f32(h, rs, P.xn, (size_t)T * N, s)) return -1;
       return all_reduce(h, (size_t)T * N, s) ? fail("prefill (exact): all-reduce failed: %s", g_last_error.c_str()) : 0;
     };
-    // one activation image per vec_dot partner (gguf/mod.rs:465-478: Q8_K rows for the K-quants, Q8_0 rows for Q8_0 weights): projections that share their input share
-    // the image when their weight formats ask for the same one (every model of BASELINE.json's configs: one image per group)
-    auto group = [&](std::initializer_list<const GgufMatMul *> ms, std::initializer_list<int> Ns, std::initializer_list<float *> outs, int K, const float *x, const float *x2, int ldx,
-                     const float *nw, float *xtmp, int acc) -> int {
-      std::vector<const GgufMatMul *> m(ms);
-      std::vector<int> n(Ns);
-      std::vector<float *> o(outs);
-      std::vector<bool> done(m.size(), false);
-      for (size_t i = 0; i < m.size(); ++i) {
-        if (done[i]) continue;
-        const int ty = m[i]->get_qtensor()->dtype, mode = ty == Q8_0 ? 1 : 0;
-        if (mrs_qi_quantize_for(ty, x, x2, ldx, nw, cfg.rms_eps, T, K, qact, xtmp, s)) return fail("prefill (exact): activation quantizer refused K=%d (ggml dtype %d)", K, ty);
-        for (size_t j = i; j < m.size(); ++j)
-          if (!done[j] && ((m[j]->get_qtensor()->dtype == Q8_0) ? 1 : 0) == mode) { if (lin(*m[j], n[j], K, o[j], acc)) return -1; done[j] = true; }
-      }
-      return 0;
+    // one activation image per vec_dot partner (gguf/mod.rs:465-478: Q8_K rows for the K-quants, Q8_0 rows for Q8_0 weights): projections that share their input h share
+    // the image of RmsNorm(h) when their weight formats ask for the same one (every model of BASELINE.json's configs: one image per group); the image precedes its GEMMs
+    auto group = [&](std::initializer_list<Proj> ps, const float *nw) -> int {
+      return by_format(ps, [](int ty) { return ty == Q8_0; }, [&](const std::vector<Proj> &grp) -> int {
+        const int ty = grp[0].dtype();
+        if (mrs_qi_quantize_for(ty, h, nullptr, d, nw, cfg.rms_eps, T, d, P.qact, nullptr, s)) return fail("prefill (exact): activation quantizer refused K=%d (ggml dtype %d)", d, ty);
+        for (const Proj &p : grp) if (lin(*p.m, p.n, d, p.out, 0)) return -1;
+        return 0;
+      });
     };
     if (wte->embedding_forward_raw(pa.token_ids, T, h, s)) return -1;
-    for (size_t li = 0; li < blocks.size(); ++li) {
-      const Block &bl = blocks[li];
-      if (group({bl.q_proj.get(), bl.k_proj.get(), bl.v_proj.get()}, {nq, nkv, nkv}, {q, k, v}, d, h, nullptr, d, bl.input_layernorm, nullptr, 0)) return -1;
-      rotary_embedding_positions(q, k, (void *)bufs.cos_table, (void *)bufs.sin_table, (void *)pa.positions, cfg.rope_interleaved ? 0 : 1, hd, T,
-                                 cfg.rot_dim / 2, cfg.max_context_len, cfg.num_heads, cfg.num_kv_heads, nq, nkv, 2, st);
-      reshape_and_cache(k, v, bl.key_cache, bl.value_cache, (int64_t *)pa.slot_mapping, T, cfg.num_kv_heads, hd, bs, 8, nkv, nkv, s, 2, kvd == 1 ? 1 : 0, nullptr, nullptr);
-      if (mrs_prefill_attention_exact(q, bl.key_cache, bl.value_cache, pa.block_tables, pa.context_lens, attn, T, cfg.num_heads, kvh, hd, bs, nq, kvh * hd * bs, hd * bs,
-                                      1.0f / sqrtf((float)hd), eff_max, kvd, cfg.sliding_window, pa.start_pos + T, s))
+    for (const Block &bl : blocks) {
+      if (group({{bl.q_proj.get(), nq, P.q}, {bl.k_proj.get(), nkv, P.k}, {bl.v_proj.get(), nkv, P.v}}, bl.input_layernorm)) return -1;
+      rope_and_cache(bl, P.q, P.k, P.v, nq, nkv, ag.kvd == 1 ? 1 : 0, pa, T, s);
+      if (mrs_prefill_attention_exact(P.q, bl.key_cache, bl.value_cache, pa.block_tables, pa.context_lens, P.attn, T, cfg.num_heads, cfg.num_kv_heads, hd, cfg.block_size, nq,
+                                      ag.block_stride, ag.head_stride, ag.scale, ag.eff_max, ag.kvd, cfg.sliding_window, pa.start_pos + T, s))
         return fail("prefill (exact): attention refused the shape");
-      if (row_parallel(*bl.o_proj, d, nq, attn, nullptr, nq, nullptr)) return -1;
+      if (row_parallel(*bl.o_proj, d, nq, P.attn, nullptr, nq, nullptr)) return -1;
       if (cfg.num_experts > 0) {
-        if (moe_ffn_exact(bl, T, h, g, u, act, qact, mx, s)) return -1;
+        if (moe_ffn_exact(bl, P, T, s)) return -1;
         continue;
       }
-      if (group({bl.gate_proj.get(), bl.up_proj.get()}, {ff, ff}, {g, u}, d, h, nullptr, d, bl.post_attention_layernorm, nullptr, 0)) return -1;
-      if (row_parallel(*bl.down_proj, d, ff, g, u, ff, act)) return -1;
+      if (group({{bl.gate_proj.get(), ff, P.g}, {bl.up_proj.get(), ff, P.u}}, bl.post_attention_layernorm)) return -1;
+      if (row_parallel(*bl.down_proj, d, ff, P.g, P.u, ff, P.act)) return -1;
     }
     // ctx.logits: only the last prompt token reaches lm_head (llama.rs:514-517): the decode engine's final norm + lm_head launch
     if (mrs_dec_proj(&dlm_head, cfg.vocab_size, nullptr, h + (size_t)(T - 1) * d, d, ln_f, cfg.rms_eps, pa.logits, cfg.vocab_size, 0, 1.0f, nullptr, 1, s))
       return fail("prefill (exact): lm_head refused");
     return 0;
   }
-  int prefill(const mrs_llama_prefill_args &pa, int T, hipStream_t s) const {
-    if (T <= 0) return fail("prefill: T must be positive");
-    const int start_pos = pa.start_pos;
-    if (!wte || !lm_head || !ln_f) return fail("model is missing token_embd / output / output_norm");
-    if (pa.workspace_bytes < prefill_workspace_bytes(cfg, T)) return fail("prefill workspace too small");
+
+  // ---- round 6: every dense linear has a bf16 shadow copy -> the prompt GEMMs are plain bf16 library GEMMs (ext_gemm_lt.hip: hipBLASLt), the activations bf16 ROWS;
+  //      same arithmetic as the fused-dequant kernels of prefill_dequant (weights rounded to bf16 once, f32 accumulation) in the library's summation order.  prefill_mode 2
+  //      forces the fused-dequant kernels (A / B).
+  struct LtFns {  // optional entry points of ext_gemm_lt.hip (absent from the host-emulation build), resolved once
+    int (*gemm)(const void *, const void *, float *, int, int, int, int, int, void *) = (decltype(gemm))lookup_quiet("mrs_lt_gemm_bf16");
+    int (*rows)(const float *, int, int, int, void *, void *) = (decltype(rows))lookup_quiet("mrs_rows_f32_to_bf16");
+    int (*glu)(const float *, const float *, int, int, int, void *, void *) = (decltype(glu))lookup_quiet("mrs_rows_glu_bf16");
+    int (*norm)(const float *, const float *, int, int, float, void *, void *) = (decltype(norm))lookup_quiet("mrs_rows_rms_norm_bf16");
+    bool ok() const { return gemm && rows && glu && norm; }
+  };
+  static const LtFns &lt() { static const LtFns f; return f; }
+  bool shadow_selected(int T) const {
+    const int d = cfg.hidden_size, nq = cfg.num_heads * cfg.head_dim, ff = cfg.intermediate_size;
+    return T > prefill_big_min && bf16_shadow_ok() && prefill_mode != 2 && lt().ok() && cfg.num_experts == 0 && cfg.head_dim == 128 && cfg.block_size == 32 &&
+           d % 8 == 0 && nq % 8 == 0 && ff % 8 == 0;
+  }
+  int prefill_shadow(const PrefillBufs &P, const mrs_llama_prefill_args &pa, int T, hipStream_t s) const {
     const int d = cfg.hidden_size, hd = cfg.head_dim, nq = cfg.num_heads * hd, nkv = cfg.num_kv_heads * hd, ff = cfg.intermediate_size;
-    const size_t t = (size_t)T;
-    char *p = (char *)(((uintptr_t)pa.workspace + 255) & ~(uintptr_t)255);
-    auto take = [&](size_t n) { char *r = p; p += align(n); return r; };
-    float *h = (float *)take(t * d * 4), *xn = (float *)take(t * d * 4);
-    float *q = (float *)take(t * nq * 4), *attn = (float *)take(t * nq * 4);
-    float *k = (float *)take(t * nkv * 4), *v = (float *)take(t * nkv * 4);
-    float *g = (float *)take(t * ff * 4), *u = (float *)take(t * ff * 4), *act = (float *)take(t * ff * 4);
-    if (prefill_exact_ok()) {
-      void *qact = take(mrs_qi_act_bytes(T, std::max(std::max(d, nq), ff)));
-      const size_t qws_bytes = mrs_gemm_qi_workspace_bytes(T, std::max(d, nq));
-      void *qws = take(qws_bytes);
-      MoeExactBufs mx{};
-      if (cfg.num_experts > 0) {  // routes = T * top_k rows in expert-sorted order; g / u / act become [routes][ff]
-        const size_t tk = (size_t)cfg.num_experts_per_tok, r = t * tk, E = (size_t)cfg.num_experts;
-        g = (float *)take(r * ff * 4); u = (float *)take(r * ff * 4); act = (float *)take(r * ff * 4);
-        mx.ids = (int32_t *)take(r * 4); mx.w = (float *)take(r * 4); mx.sorted = (int32_t *)take(r * 4); mx.inv = (int32_t *)take(r * 4);
-        mx.bounds = (int32_t *)take((E + 1) * 4); mx.counts = (int32_t *)take(E * 4); mx.cursors = (int32_t *)take(E * 4);
-        mx.y = (float *)take(r * d * 4);
-        mx.qact_g = take(mrs_qi_act_bytes((int)r, d)); mx.qact_r = take(mrs_qi_act_bytes((int)r, ff));
-      }
-      return prefill_exact(pa, T, h, xn, q, k, v, attn, g, u, act, qact, qws, qws_bytes, mx, s);
+    const AttnGeom ag = attn_geom();
+    const LtFns &L = lt();
+    float *h = P.h, *g = P.g, *u = P.u;
+    void *xb = P.xb;
+    auto lgemm_at = [&](const void *wb, int N, int K, float *out, int ldo, int acc) -> int {
+      const int rc = L.gemm(wb, xb, out, ldo, N, K, T, acc, s);
+      return rc ? fail("prefill (bf16 shadow): library GEMM refused N=%d K=%d T=%d (%d)", N, K, T, rc) : 0;
+    };
+    auto lgemm = [&](const GgufMatMul &m, int N, int K, float *out, int acc) -> int { return lgemm_at(m.get_qtensor()->bf16, N, K, out, N, acc); };
+    if (wte->embedding_forward_raw(pa.token_ids, T, h, s)) return -1;
+    for (size_t li = 0; li < blocks.size(); ++li) {
+      const Block &bl = blocks[li];
+      if (!bl.q_proj || !bl.key_cache) return fail("layer %zu is incomplete", li);
+      if (L.norm(h, bl.input_layernorm, T, d, cfg.rms_eps, xb, s)) return fail("prefill (bf16 shadow): hidden size must be a multiple of 8");
+      // q / k / v (and gate / up) shadow rows laid out back to back by the loader (llama.py) = ONE GEMM of N = nq + 2 nkv (2 ff) rows: the role of fast_mmq::fused_qkv /
+      // fused_glu (one launch per shared input); the outputs are column ranges of one [T][N] buffer, which rotary / reshape_and_cache / the attention kernel take by stride
+      const char *qb = (const char *)bl.q_proj->get_qtensor()->bf16, *kb = (const char *)bl.k_proj->get_qtensor()->bf16, *vb = (const char *)bl.v_proj->get_qtensor()->bf16;
+      const bool qkv_fused = kb == qb + (size_t)nq * d * 2 && vb == kb + (size_t)nkv * d * 2 && (size_t)(nq + 2 * nkv) <= (size_t)ff;
+      float *qp = P.q, *kp = P.k, *vp = P.v;
+      int qs = nq, ks = nkv;
+      if (qkv_fused) {
+        const int nqkv = nq + 2 * nkv;
+        if (lgemm_at(qb, nqkv, d, g, nqkv, 0)) return -1;  // g [T][ff] is free until the FFN
+        qp = g; kp = g + nq; vp = g + nq + nkv; qs = ks = nqkv;
+      } else if (lgemm(*bl.q_proj, nq, d, P.q, 0) || lgemm(*bl.k_proj, nkv, d, P.k, 0) || lgemm(*bl.v_proj, nkv, d, P.v, 0)) return -1;
+      rope_and_cache(bl, qp, kp, vp, qs, ks, 1, pa, T, s);
+      if (mrs_prefill_attention_window_f32_bf16(qp, bl.key_cache, bl.value_cache, pa.block_tables, P.attn, T, pa.start_pos, cfg.num_heads, cfg.num_kv_heads, hd, cfg.block_size, qs, nq,
+                                                ag.block_stride, ag.head_stride, ag.scale, cfg.sliding_window, s) != 0)
+        return fail("prefill (bf16 shadow): the MFMA flash attention refused the shape (head_dim 128, block 32)");
+      if (L.rows(P.attn, nq, T, nq, xb, s)) return -1;
+      if (residual_gemm([&](float *out, int acc) { return lgemm(*bl.o_proj, d, nq, out, acc); }, P, T, s)) return -1;
+      if (L.norm(h, bl.post_attention_layernorm, T, d, cfg.rms_eps, xb, s)) return -1;
+      const char *gb = (const char *)bl.gate_proj->get_qtensor()->bf16, *ub = (const char *)bl.up_proj->get_qtensor()->bf16;
+      if (ub == gb + (size_t)ff * d * 2 && P.gate_up_adjacent(T, ff)) {  // one GEMM of 2 ff rows into [T][2 ff] = the g and u buffers
+        if (lgemm_at(gb, 2 * ff, d, g, 2 * ff, 0) || L.glu(g, g + ff, 2 * ff, T, ff, xb, s)) return -1;
+      } else if (lgemm(*bl.gate_proj, ff, d, g, 0) || lgemm(*bl.up_proj, ff, d, u, 0) || L.glu(g, u, ff, T, ff, xb, s)) return -1;
+      if (residual_gemm([&](float *out, int acc) { return lgemm(*bl.down_proj, d, ff, out, acc); }, P, T, s)) return -1;
     }
-    MoePrefillBufs moe{};
-    if (cfg.num_experts > 0) {
-      const size_t tk = (size_t)cfg.num_experts_per_tok, r = t * tk, E = (size_t)cfg.num_experts;
-      moe.g = (float *)take(r * ff * 4); moe.u = (float *)take(r * ff * 4); moe.act = (float *)take(r * ff * 4);
-      moe.ids = (int32_t *)take(r * 4); moe.w = (float *)take(r * 4); moe.sorted = (int32_t *)take(r * 4);
-      moe.bounds = (int32_t *)take((E + 1) * 4); moe.counts = (int32_t *)take(E * 4); moe.cursors = (int32_t *)take(E * 4);
-      moe.y_in = take(t * (pad_to(d, MATRIX_ROW_PADDING) / 32) * 36);
-      moe.y_act = take(r * (pad_to(ff, MATRIX_ROW_PADDING) / 32) * 36);
-      moe.sum = (float *)take(t * d * 4);
-      if (T > prefill_big_min) { moe.xb = take(t * d * 2); moe.yb = take(r * ff * 2); }
-    }
+    if (!mrs_decode_gemv_supported(lm_head->get_qtensor()->dtype)) return fail("prefill (bf16 shadow): lm_head dtype %d", lm_head->get_qtensor()->dtype);
+    return last_token_logits(P, pa, T, s);
+  }
+
+  // ---- fused block-dequant bf16 MFMA GEMMs on the GGUF blocks.  T > prefill_big_min: the 256-row-tile kernel over bf16 activation slabs (converted once per GEMM
+  //      group), split-K partials in `part`; shorter prompts: the 128-row f32-activation kernel
+  int prefill_dequant(const PrefillBufs &P, const mrs_llama_prefill_args &pa, int T, hipStream_t s) const {
+    const int d = cfg.hidden_size, hd = cfg.head_dim, nq = cfg.num_heads * hd, nkv = cfg.num_kv_heads * hd, ff = cfg.intermediate_size;
+    const int bs = cfg.block_size, kvh = cfg.num_kv_heads;
+    const AttnGeom ag = attn_geom();
     const int64_t st = (int64_t)(intptr_t)s;
-    // T > prefill_big_min: the 256-row-tile kernel over bf16 activations (converted once per GEMM group), split-K partials in `part`
     const bool big = T > prefill_big_min;
-    const size_t part_bytes = big ? mrs_gemm_q_bf16_workspace_bytes(T) : 0;
-    void *xb = big ? take(t * std::max(std::max(d, nq), ff) * 2) : nullptr, *part = big ? take(part_bytes) : nullptr;
+    float *h = P.h, *xn = P.xn, *q = P.q, *attn = P.attn;
+    void *xb = P.xb;
     const float *xb_src = nullptr;    // which f32 buffer xb currently mirrors (within one GEMM group)
     const float *xb_ready = nullptr;  // set by a producer that wrote the slabs of that (never materialised) f32 buffer directly
     auto to_bf16 = [&](const float *x, int K) -> int {
@@ -803,138 +888,49 @@ class Llama {
       if (xb_ready == x) { xb_ready = nullptr; return 0; }
       return mrs_convert_f32_bf16_slabs(x, K, T, K, xb, s);
     };
-    auto gemm = [&](const GgufMatMul &m, const float *x, int K, float *out, int N, int acc) -> int {
-      const QTensor *w = m.get_qtensor();
-      int rc;
-      if (big) {
-        xb_src = nullptr;
-        rc = to_bf16(x, K);
-        if (!rc) rc = mrs_gemm_q_bf16_multi(1, &w->data, &N, &out, &N, w->dtype, K, xb, T, acc, part, part_bytes, s);
-        xb_src = nullptr;
-      } else rc = mrs_gemm_q_f32(w->data, w->dtype, N, K, x, K, out, N, T, acc, s);
-      if (rc) return fail("prefill: no GEMM for ggml dtype %d (K=%d)", w->dtype, K);
-      return 0;
-    };
-    // projections that share their input run as ONE launch per weight type (fast_mmq::fused_qkv / fused_glu role)
-    auto gemm_multi = [&](std::initializer_list<const GgufMatMul *> ms, const float *x, int K, std::initializer_list<float *> outs,
-                          std::initializer_list<int> Ns) -> int {
-      std::vector<const GgufMatMul *> m(ms);
-      std::vector<float *> o(outs);
-      std::vector<int> n(Ns);
-      std::vector<bool> done(m.size(), false);
+    // projections that share their input run as ONE launch per weight type (fast_mmq::fused_qkv / fused_glu role); a single projection is a group of one
+    auto gemm = [&](std::initializer_list<Proj> ps, const float *x, int K, int acc) -> int {
       xb_src = nullptr;
-      for (size_t i = 0; i < m.size(); ++i) {
-        if (done[i]) continue;
-        const int ty = m[i]->get_qtensor()->dtype;
-        const void *w[3]; float *oo[3]; int nn[3], ld[3], c = 0;
-        for (size_t j = i; j < m.size(); ++j)
-          if (!done[j] && m[j]->get_qtensor()->dtype == ty) {
-            w[c] = m[j]->get_qtensor()->data;
-            oo[c] = o[j]; nn[c] = n[j]; ld[c] = n[j]; ++c; done[j] = true;
-          }
+      const int rc = by_format(ps, [](int ty) { return ty; }, [&](const std::vector<Proj> &grp) -> int {
+        const int ty = grp[0].dtype(), c = (int)grp.size();
+        const void *w[3]; float *oo[3]; int nn[3];  // ld = n: dense outputs
+        for (int i = 0; i < c; ++i) { w[i] = grp[i].m->get_qtensor()->data; oo[i] = grp[i].out; nn[i] = grp[i].n; }
         int rc;
         if (big) {
           rc = to_bf16(x, K);
-          if (!rc) rc = mrs_gemm_q_bf16_multi(c, w, nn, oo, ld, ty, K, xb, T, 0, part, part_bytes, s);
-        } else rc = mrs_gemm_q_f32_multi(c, w, nn, oo, ld, ty, K, x, K, T, 0, s);
-        if (rc) return fail("prefill: no GEMM for ggml dtype %d (K=%d)", ty, K);
-      }
+          if (!rc) rc = mrs_gemm_q_bf16_multi(c, w, nn, oo, nn, ty, K, xb, T, acc, P.part, P.part_bytes, s);
+        } else rc = mrs_gemm_q_f32_multi(c, w, nn, oo, nn, ty, K, x, K, T, acc, s);
+        return rc ? fail("prefill: no GEMM for ggml dtype %d (K=%d)", ty, K) : 0;
+      });
       xb_src = nullptr;
-      return 0;
+      return rc;
     };
     if (wte->embedding_forward_raw(pa.token_ids, T, h, s)) return -1;
-    const int bs = cfg.block_size, kvh = cfg.num_kv_heads;
-    const int eff_max = std::min(cfg.max_blocks_per_seq * bs, cfg.max_context_len);
-    const int parts = (eff_max + 511) / 512;
-    // ---- round 6: every dense linear has a bf16 shadow copy -> the prompt GEMMs are plain bf16 library GEMMs (ext_gemm_lt.hip: hipBLASLt), the activations bf16 ROWS;
-    //      same arithmetic as the fused-dequant kernels below (weights rounded to bf16 once, f32 accumulation) in the library's summation order.  prefill_mode 2 forces the
-    //      fused-dequant kernels (A / B).
-    typedef int (*lt_gemm_fn)(const void *, const void *, float *, int, int, int, int, int, void *);
-    typedef int (*lt_rows_fn)(const float *, int, int, int, void *, void *);
-    typedef int (*lt_glu_fn)(const float *, const float *, int, int, int, void *, void *);
-    typedef int (*lt_norm_fn)(const float *, const float *, int, int, float, void *, void *);
-    static const lt_gemm_fn lt_gemm = (lt_gemm_fn)lookup_quiet("mrs_lt_gemm_bf16");
-    static const lt_rows_fn lt_rows = (lt_rows_fn)lookup_quiet("mrs_rows_f32_to_bf16");
-    static const lt_glu_fn lt_glu = (lt_glu_fn)lookup_quiet("mrs_rows_glu_bf16");
-    static const lt_norm_fn lt_norm = (lt_norm_fn)lookup_quiet("mrs_rows_rms_norm_bf16");
-    if (big && bf16_shadow_ok() && prefill_mode != 2 && lt_gemm && lt_rows && lt_glu && lt_norm && cfg.num_experts == 0 && cfg.head_dim == 128 && cfg.block_size == 32 &&
-        d % 8 == 0 && nq % 8 == 0 && ff % 8 == 0) {
-      auto lgemm_at = [&](const void *wb, int N, int K, float *out, int ldo, int acc) -> int {
-        const int rc = lt_gemm(wb, xb, out, ldo, N, K, T, acc, s);
-        return rc ? fail("prefill (bf16 shadow): library GEMM refused N=%d K=%d T=%d (%d)", N, K, T, rc) : 0;
-      };
-      auto lgemm = [&](const GgufMatMul &m, int N, int K, float *out, int acc) -> int { return lgemm_at(m.get_qtensor()->bf16, N, K, out, N, acc); };
-      for (size_t li = 0; li < blocks.size(); ++li) {
-        const Block &bl = blocks[li];
-        if (!bl.q_proj || !bl.key_cache) return fail("layer %zu is incomplete", li);
-        if (lt_norm(h, bl.input_layernorm, T, d, cfg.rms_eps, xb, s)) return fail("prefill (bf16 shadow): hidden size must be a multiple of 8");
-        // q / k / v (and gate / up) shadow rows laid out back to back by the loader (llama.py) = ONE GEMM of N = nq + 2 nkv (2 ff) rows: the role of fast_mmq::fused_qkv /
-        // fused_glu (one launch per shared input); the outputs are column ranges of one [T][N] buffer, which rotary / reshape_and_cache / the attention kernel take by stride
-        const char *qb = (const char *)bl.q_proj->get_qtensor()->bf16, *kb = (const char *)bl.k_proj->get_qtensor()->bf16, *vb = (const char *)bl.v_proj->get_qtensor()->bf16;
-        const bool qkv_fused = kb == qb + (size_t)nq * d * 2 && vb == kb + (size_t)nkv * d * 2 && (size_t)(nq + 2 * nkv) <= (size_t)ff;
-        float *qp = q, *kp = k, *vp = v;
-        int qs = nq, ks = nkv;
-        if (qkv_fused) {
-          const int nqkv = nq + 2 * nkv;
-          if (lgemm_at(qb, nqkv, d, g, nqkv, 0)) return -1;  // g [T][ff] is free until the FFN
-          qp = g; kp = g + nq; vp = g + nq + nkv; qs = ks = nqkv;
-        } else if (lgemm(*bl.q_proj, nq, d, q, 0) || lgemm(*bl.k_proj, nkv, d, k, 0) || lgemm(*bl.v_proj, nkv, d, v, 0)) return -1;
-        rotary_embedding_positions(qp, kp, (void *)bufs.cos_table, (void *)bufs.sin_table, (void *)pa.positions, cfg.rope_interleaved ? 0 : 1, hd, T,
-                                   cfg.rot_dim / 2, cfg.max_context_len, cfg.num_heads, cfg.num_kv_heads, qs, ks, 2, st);
-        reshape_and_cache(kp, vp, bl.key_cache, bl.value_cache, (int64_t *)pa.slot_mapping, T, cfg.num_kv_heads, hd, bs, 8, ks, ks, s, 2, 1, nullptr, nullptr);
-        if (mrs_prefill_attention_window_f32_bf16(qp, bl.key_cache, bl.value_cache, pa.block_tables, attn, T, start_pos, cfg.num_heads, kvh, hd, bs, qs, nq,
-                                                  kvh * hd * bs, hd * bs, 1.0f / sqrtf((float)hd), cfg.sliding_window, s) != 0)
-          return fail("prefill (bf16 shadow): the MFMA flash attention refused the shape (head_dim 128, block 32)");
-        if (lt_rows(attn, nq, T, nq, xb, s)) return -1;
-        if (cfg.world_size > 1) { if (lgemm(*bl.o_proj, d, nq, xn, 0) || all_reduce(xn, t * d, s) || mrs_vec_add_f32(h, xn, t * d, s)) return -1; }
-        else if (lgemm(*bl.o_proj, d, nq, h, 1)) return -1;
-        if (lt_norm(h, bl.post_attention_layernorm, T, d, cfg.rms_eps, xb, s)) return -1;
-        const char *gb = (const char *)bl.gate_proj->get_qtensor()->bf16, *ub = (const char *)bl.up_proj->get_qtensor()->bf16;
-        if (ub == gb + (size_t)ff * d * 2 && u == g + t * ff) {  // one GEMM of 2 ff rows into [T][2 ff] = the g and u buffers, which the workspace holds back to back
-          if (lgemm_at(gb, 2 * ff, d, g, 2 * ff, 0) || lt_glu(g, g + ff, 2 * ff, T, ff, xb, s)) return -1;
-        } else if (lgemm(*bl.gate_proj, ff, d, g, 0) || lgemm(*bl.up_proj, ff, d, u, 0) || lt_glu(g, u, ff, T, ff, xb, s)) return -1;
-        if (cfg.world_size > 1) { if (lgemm(*bl.down_proj, d, ff, xn, 0) || all_reduce(xn, t * d, s) || mrs_vec_add_f32(h, xn, t * d, s)) return -1; }
-        else if (lgemm(*bl.down_proj, d, ff, h, 1)) return -1;
-      }
-      const QTensor *lm = lm_head->get_qtensor();
-      if (!mrs_decode_gemv_supported(lm->dtype)) return fail("prefill (bf16 shadow): lm_head dtype %d", lm->dtype);
-      if (mrs_decode_norm_proj(lm->data, lm->dtype, cfg.vocab_size, d, h + (t - 1) * d, ln_f, cfg.rms_eps, pa.logits, cfg.vocab_size, 1, s)) return fail("prefill: lm_head refused");
-      return 0;
-    }
+    const int parts = (ag.eff_max + 511) / 512;
     const bool use_v1 = (parts == 1 || (long)T * cfg.num_heads > 512);  // paged_attention.rs:302-307 (only consulted when the MFMA flash kernel refuses the shape)
     for (size_t li = 0; li < blocks.size(); ++li) {
       const Block &bl = blocks[li];
       if (!bl.q_proj || !bl.key_cache) return fail("layer %zu is incomplete", li);
       if (big) { if (mrs_rms_norm_bf16_slabs(h, bl.input_layernorm, T, d, cfg.rms_eps, xb, s)) return fail("prefill: hidden size must be a multiple of 64"); xb_ready = xn; }
       else mrs_rms_norm_f32(h, bl.input_layernorm, xn, T, d, cfg.rms_eps, st);
-      if (gemm_multi({bl.q_proj.get(), bl.k_proj.get(), bl.v_proj.get()}, xn, d, {q, k, v}, {nq, nkv, nkv})) return -1;
-      rotary_embedding_positions(q, k, (void *)bufs.cos_table, (void *)bufs.sin_table, (void *)pa.positions, cfg.rope_interleaved ? 0 : 1, hd, T,
-                                 cfg.rot_dim / 2, cfg.max_context_len, cfg.num_heads, cfg.num_kv_heads, nq, nkv, 2, st);
-      reshape_and_cache(k, v, bl.key_cache, bl.value_cache, (int64_t *)pa.slot_mapping, T, cfg.num_kv_heads, hd, bs, 8, nkv, nkv, s, 2, 1, nullptr, nullptr);
+      if (gemm({{bl.q_proj.get(), nq, q}, {bl.k_proj.get(), nkv, P.k}, {bl.v_proj.get(), nkv, P.v}}, xn, d, 0)) return -1;
+      rope_and_cache(bl, q, P.k, P.v, nq, nkv, 1, pa, T, s);
       // causal attention over the pages just written: MFMA flash kernel (head_dim 128 / block 32), else prompt token t = "sequence" t
       // of the decode-style kernel with context_lens[t] = pos + 1
-      if (mrs_prefill_attention_window_f32_bf16(q, bl.key_cache, bl.value_cache, pa.block_tables, attn, T, start_pos, cfg.num_heads, kvh, hd, bs, nq, nq,
-                                                kvh * hd * bs, hd * bs, 1.0f / sqrtf((float)hd), cfg.sliding_window, s) != 0) {
+      if (mrs_prefill_attention_window_f32_bf16(q, bl.key_cache, bl.value_cache, pa.block_tables, attn, T, pa.start_pos, cfg.num_heads, kvh, hd, bs, nq, nq,
+                                                ag.block_stride, ag.head_stride, ag.scale, cfg.sliding_window, s) != 0) {
         if (cfg.sliding_window > 0) return fail("prefill: sliding-window attention needs the MFMA flash kernel's shapes (head_dim 128, block 32)");
         // fallback for head / block sizes outside the flash kernel: prompt token t = "sequence" t of the decode-style kernel.  v1 keeps all logits of
         // a sequence in LDS, so long contexts with few (token, head) pairs take v2 over 512-token partitions with the runner's partial buffers
-        if (use_v1) {
-          mrs_paged_attention_f32_bf16(0, attn, nullptr, nullptr, nullptr, q, bl.key_cache, bl.value_cache, nullptr, kvh, 1.0f / sqrtf((float)hd), 1.0f,
-                                       pa.block_tables, pa.context_lens, bs, eff_max, T, cfg.num_heads, hd, cfg.max_blocks_per_seq, nq, kvh * hd * bs,
-                                       hd * bs, s, nullptr);
-        } else {
-          if (T > cfg.max_batch) return fail("prefill: %d prompt tokens at max_context_len %d need the v2 attention workspace of %d sequences; use prompts of <= %d tokens or the flash-attention shapes (head_dim 128, block 32)", T, cfg.max_context_len, T, cfg.max_batch);
-          mrs_paged_attention_f32_bf16(1, attn, ws.exp_sums, ws.max_logits, ws.attn_ws, q, bl.key_cache, bl.value_cache, nullptr, kvh, 1.0f / sqrtf((float)hd), 1.0f,
-                                       pa.block_tables, pa.context_lens, bs, eff_max, T, cfg.num_heads, hd, cfg.max_blocks_per_seq, nq, kvh * hd * bs,
-                                       hd * bs, s, nullptr);
-        }
+        if (!use_v1 && T > cfg.max_batch) return fail("prefill: %d prompt tokens at max_context_len %d need the v2 attention workspace of %d sequences; use prompts of <= %d tokens or the flash-attention shapes (head_dim 128, block 32)", T, cfg.max_context_len, T, cfg.max_batch);
+        mrs_paged_attention_f32_bf16(use_v1 ? 0 : 1, attn, use_v1 ? nullptr : ws.exp_sums, use_v1 ? nullptr : ws.max_logits, use_v1 ? nullptr : ws.attn_ws, q, bl.key_cache, bl.value_cache,
+                                     nullptr, kvh, ag.scale, 1.0f, pa.block_tables, pa.context_lens, bs, ag.eff_max, T, cfg.num_heads, hd, cfg.max_blocks_per_seq, nq, ag.block_stride,
+                                     ag.head_stride, s, nullptr);
       }
-      if (cfg.world_size > 1) {  // row-parallel: partial -> all-reduce -> residual add (bias-free)
-        if (gemm(*bl.o_proj, attn, nq, xn, d, 0) || all_reduce(xn, t * d, s) || mrs_vec_add_f32(h, xn, t * d, s)) return -1;
-      } else if (gemm(*bl.o_proj, attn, nq, h, d, 1)) return -1;
+      if (residual_gemm([&](float *out, int acc) { return gemm({{bl.o_proj.get(), d, out}}, attn, nq, acc); }, P, T, s)) return -1;
       if (cfg.num_experts > 0) {
         if (!bl.router || !bl.gate_exps.data || !bl.up_exps.data || !bl.down_exps.data) return fail("layer %zu has no experts", li);
-        if (moe_ffn_prefill(bl, h, xn, T, moe, s)) return -1;
+        if (moe_ffn_prefill(bl, P, T, s)) return -1;
         continue;
       }
       if (big) { if (mrs_rms_norm_bf16_slabs(h, bl.post_attention_layernorm, T, d, cfg.rms_eps, xb, s)) return -1; xb_ready = xn; }
@@ -942,30 +938,27 @@ class Llama {
       // two GEMM segments + the 12.7 us GLU pass: the one-launch gate / up / SiLU*up GEMM (mrs_gemm_q_bf16_glu) is bit-identical but was measured 1.5-2.5 % SLOWER
       // per prompt on the MI355X (TTFT 14.15 vs 13.82 ms at 512 tokens, 47.5 vs 46.9 ms at 2048: the epilogue's expf and 2-byte half-line stores sit in the
       // un-overlapped tail of every workgroup)
-      if (gemm_multi({bl.gate_proj.get(), bl.up_proj.get()}, xn, d, {g, u}, {ff, ff})) return -1;
-      if (big && ff % 64 == 0) { if (mrs_glu_bf16_slabs(g, u, ff, T, ff, 0, xb, s)) return -1; xb_ready = act; }
-      else fused_glu_f32(g, u, act, (uint32_t)T, (uint32_t)ff, (uint32_t)ff, (uint32_t)ff, 0, s);
-      if (cfg.world_size > 1) {
-        if (gemm(*bl.down_proj, act, ff, xn, d, 0) || all_reduce(xn, t * d, s) || mrs_vec_add_f32(h, xn, t * d, s)) return -1;
-      } else if (gemm(*bl.down_proj, act, ff, h, d, 1)) return -1;
+      if (gemm({{bl.gate_proj.get(), ff, P.g}, {bl.up_proj.get(), ff, P.u}}, xn, d, 0)) return -1;
+      if (big && ff % 64 == 0) { if (mrs_glu_bf16_slabs(P.g, P.u, ff, T, ff, 0, xb, s)) return -1; xb_ready = P.act; }
+      else fused_glu_f32(P.g, P.u, P.act, (uint32_t)T, (uint32_t)ff, (uint32_t)ff, (uint32_t)ff, 0, s);
+      if (residual_gemm([&](float *out, int acc) { return gemm({{bl.down_proj.get(), d, out}}, P.act, ff, acc); }, P, T, s)) return -1;
     }
-    // ctx.logits: only the last prompt token reaches lm_head (llama.rs:514-517)
-    const QTensor *lm = lm_head->get_qtensor();
-    if (mrs_decode_gemv_supported(lm->dtype)) {
-      if (mrs_decode_norm_proj(lm->data, lm->dtype, cfg.vocab_size, d, h + (t - 1) * d, ln_f, cfg.rms_eps, pa.logits, cfg.vocab_size, 1, s))
-        return fail("prefill: lm_head refused");
-    } else {
-      mrs_rms_norm_f32(h + (t - 1) * d, ln_f, xn, 1, d, cfg.rms_eps, st);
-      const Scratch sc{take((size_t)(pad_to(d, MATRIX_ROW_PADDING) / 32) * 36), (size_t)(pad_to(d, MATRIX_ROW_PADDING) / 32) * 36};
-      if (lm_head->forward_raw(xn, 1, pa.logits, sc, s)) return -1;
-    }
-    return 0;
+    return last_token_logits(P, pa, T, s);
+  }
+
+  int prefill(const mrs_llama_prefill_args &pa, int T, hipStream_t s) const {
+    if (T <= 0) return fail("prefill: T must be positive");
+    if (!wte || !lm_head || !ln_f) return fail("model is missing token_embd / output / output_norm");
+    PrefillBufs P;
+    if (pa.workspace_bytes < lay_out_prefill(cfg, T, pa.workspace, P) + WORKSPACE_SLACK) return fail("prefill workspace too small");
+    if (prefill_exact_ok()) return prefill_exact(P, pa, T, s);
+    return shadow_selected(T) ? prefill_shadow(P, pa, T, s) : prefill_dequant(P, pa, T, s);
   }
   double prefill_flops(int T) const {
     double w = 0;
     for (const Block &bl : blocks)
-      for (const auto *m : {&bl.q_proj, &bl.k_proj, &bl.v_proj, &bl.o_proj, &bl.gate_proj, &bl.up_proj, &bl.down_proj})
-        if (*m) w += (double)(*m)->get_qtensor()->rows * (double)(*m)->get_qtensor()->cols;
+      for (const GgufMatMul *m : bl.dense())
+        if (m) w += (double)m->get_qtensor()->rows * (double)m->get_qtensor()->cols;
     double f = 2.0 * T * w;
     if (cfg.num_experts > 0)  // every token visits top-k experts: gate, up, down of [ffn x hidden] each (the router's E x hidden GEMV is negligible)
       f += 2.0 * T * (double)cfg.num_experts_per_tok * 3.0 * (double)cfg.intermediate_size * (double)cfg.hidden_size * (double)blocks.size();
@@ -1019,8 +1012,8 @@ class Llama {
   double decode_bytes(int b, int ctx) const {
     double t = 0;
     for (const Block &bl : blocks)
-      for (const auto *m : {&bl.q_proj, &bl.k_proj, &bl.v_proj, &bl.o_proj, &bl.gate_proj, &bl.up_proj, &bl.down_proj})
-        if (*m) t += (double)(*m)->get_qtensor()->nbytes();
+      for (const GgufMatMul *m : bl.dense())
+        if (m) t += (double)m->get_qtensor()->nbytes();
     if (cfg.num_experts > 0)  // per token only the top-k experts of every layer are streamed (+ the router)
       for (const Block &bl : blocks)
         t += (double)b * cfg.num_experts_per_tok * (double)(bl.gate_exps.nbytes() + bl.up_exps.nbytes() + bl.down_exps.nbytes()) / cfg.num_experts +
