@@ -85,6 +85,31 @@ int mrs_dec_attention(float *out_f32, void *img_out, unsigned *ticket, float *pa
                       const void *v_cache, int num_kv_heads, float scale, const uint32_t *block_tables, const uint32_t *context_lens, int block_size,
                       int max_context_len, int num_seqs, int num_heads, int head_size, int max_blocks_per_seq, int q_stride, int kv_block_stride,
                       int kv_head_stride, int kv_dtype, int sliding_window /* > 0: attend the last W positions only (Mistral), 0 = all */, void *stream);
+/* FP8 (E4M3, OCP "FN": no infinities, max 448) KV pages for the decode engine and the exact prompt path.  Pages are bytes in the reference's FP8 layout -- K
+ * [blocks][kv heads][head_dim / 16][block_size][16], V [blocks][kv heads][head_dim][block_size] -- with one static f32 scale per tensor (1.0 = uncalibrated,
+ * paged_attention.rs Fp8AttentionScales).  Store: code = float_to_fp8_e4m3(x / scale) (IEEE f32 division, round to nearest even, saturate to +-448, NaN -> 0x7f | sign:
+ * the byte reshape_and_cache(cache_dtype 3) writes).  Load: f32(fp8_e4m3_to_float(code) * scale), then every operation of the 16-bit kernels in the same order.
+ * Each *_f8 entry is its counterpart's argument list without kv_dtype and with `float k_scale, float v_scale` in front of `stream` (by value: graph-capturable without
+ * a device read); strides count elements (= bytes); -1 for a scale that is not finite and > 0. */
+int mrs_dec_qkv_f8(const mrs_dec_mat *wq, const mrs_dec_mat *wk, const mrs_dec_mat *wv, const float *h, int ldh, const float *norm_w, float eps, float *q_out,
+                   void *k_cache, void *v_cache, const int64_t *slot_mapping, const int32_t *positions, const float *cos_t, const float *sin_t, int head_dim,
+                   int rot_pairs, int num_kv_heads, int block_size, int b, float k_scale, float v_scale, void *stream);
+int mrs_dec_qkv_neox_f8(const mrs_dec_mat *wq, const mrs_dec_mat *wk, const mrs_dec_mat *wv, const float *h, int ldh, const float *norm_w, float eps, float *q_out,
+                        void *k_cache, void *v_cache, const int64_t *slot_mapping, const int32_t *positions, const float *cos_t, const float *sin_t, int head_dim,
+                        int rot_pairs, int num_kv_heads, int block_size, int b, float k_scale, float v_scale, void *stream);
+int mrs_dec_qkv_img_f8(const mrs_dec_mat *wq, const mrs_dec_mat *wk, const mrs_dec_mat *wv, const void *x_img, float *q_out, void *k_cache, void *v_cache,
+                       const int64_t *slot_mapping, const int32_t *positions, const float *cos_t, const float *sin_t, int head_dim, int rot_pairs,
+                       int num_kv_heads, int block_size, int b, int neox, float k_scale, float v_scale, void *stream);
+int mrs_dec_mm_qkv_f8(const void *qi_q, int type_q, int nq, const void *qi_k, int type_k, int nk, const void *qi_v, int type_v, int nv, int k, const void *x_img,
+                      float *q_out, void *k_cache, void *v_cache, const int64_t *slot_mapping, const int32_t *positions, const float *cos_t, const float *sin_t,
+                      int head_dim, int rot_pairs, int num_kv_heads, int block_size, int b, float k_scale, float v_scale, void *stream);
+int mrs_dec_attention_f8(float *out_f32, void *img_out, unsigned *ticket, float *part_o, float *part_m, float *part_l, const float *q, const void *k_cache,
+                         const void *v_cache, int num_kv_heads, float scale, const uint32_t *block_tables, const uint32_t *context_lens, int block_size,
+                         int max_context_len, int num_seqs, int num_heads, int head_size, int max_blocks_per_seq, int q_stride, int kv_block_stride,
+                         int kv_head_stride, int sliding_window, float k_scale, float v_scale, void *stream);
+int mrs_prefill_attention_exact_f8(const float *q, const void *k_cache, const void *v_cache, const uint32_t *block_table, const uint32_t *context_lens, float *out,
+                                   int T, int num_heads, int num_kv_heads, int head_size, int block_size, int q_stride, int kv_block_stride, int kv_head_stride,
+                                   float scale, int max_context_len, int sliding_window, int max_prompt_ctx, float k_scale, float v_scale, void *stream);
 size_t mrs_dec_proj_img_max_bytes(void); /* largest activation image mrs_dec_proj_img takes (the LDS budget) */
 /* GEMV on a pre-quantized activation image: Q8_K quantization for K-quant weights (what mrs_dec_attention writes), Q8_0 for Q8_0 weights (mrs_dec_act_image with that
  * weight type); the image carries no tag -- the caller pairs image and weight */
@@ -220,7 +245,8 @@ typedef struct {
   int32_t world_size, rank;   /* tensor parallel (1, 0 = single GPU) */
   int32_t num_experts;        /* 0 = dense FFN; > 0: Mixtral-style sparse MoE FFN in every layer (models/mixtral.rs:236-304) */
   int32_t num_experts_per_tok; /* top-k of the router (softmax over all experts -> top-k -> renormalise) */
-  int32_t kv_f16;             /* decode engine only: 1 = f16 KV pages (the reference CPU path's default KV dtype, kv_cache/mod.rs:66-89), 0 = bf16 */
+  int32_t kv_f16;             /* page dtype code, decode engine only beyond 0: 0 = bf16, 1 = f16 KV pages (the reference CPU path's default KV dtype,
+                                 kv_cache/mod.rs:66-89), 2 = FP8 E4M3 bytes with per-layer static scales (mrs_llama_set_kv_scales; engine decode + exact prompt path) */
   int32_t sliding_window;     /* > 0: Mistral sliding-window attention -- a query attends the last W positions, itself included (GGUF
                                  <arch>.attention.sliding_window, gguf/normal_config.rs:792-796); decode engine + MFMA prefill only; 0 = full causal */
 } mrs_llama_config;
@@ -304,6 +330,8 @@ void mrs_llama_destroy(void *model);
  * given as [E * rows_per_expert, cols] (rank-3 GGUF tensors flattened over the expert axis) */
 int mrs_llama_set_tensor(void *model, const char *name, const void *dev_ptr, int ggml_type, int64_t n_rows, int64_t n_cols);
 int mrs_llama_set_kv_cache(void *model, int layer, void *key_cache, void *value_cache);
+/* FP8 pages (kv_f16 == 2): the static scales of one layer (default 1.0 each); finite and > 0.  They are launch arguments: a captured decode graph keeps the old ones. */
+int mrs_llama_set_kv_scales(void *model, int layer, float k_scale, float v_scale);
 int mrs_llama_set_buffers(void *model, const mrs_llama_buffers *bufs);
 /* one decode step for b sequences: embedding -> L x Block -> norm -> lm_head -> greedy sample + state advance */
 int mrs_llama_decode_step(void *model, int b, void *stream);

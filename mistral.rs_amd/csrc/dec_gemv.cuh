@@ -9,7 +9,7 @@ namespace mrs {
 namespace dec {
 using namespace mrs::dec2;
 
-enum : int { EPI_STORE = 0, EPI_RESID = 1, EPI_GLU = 2, EPI_QKV = 3, EPI_RESID2 = 4 };
+enum : int { EPI_STORE = 0, EPI_RESID = 1, EPI_GLU = 2, EPI_QKV = 3, EPI_RESID2 = 4, EPI_QKV_F8 = 5 /* EPI_QKV writing FP8 pages: its own instantiations */ };
 
 struct GemvArgs {
   Mat m[3];
@@ -56,8 +56,9 @@ __host__ __device__ constexpr int tmask_of(int type) { return type == T_Q4_K ? T
 
 template <int N> struct AuxV { float a[N], b[N]; };
 
-template <int NCOLS, int EPI, int TMASK, bool RING2>
+template <int NCOLS, int EPI_, int TMASK, bool RING2>
 __device__ __forceinline__ void gemv_phase(const GemvArgs &a, char *smem, float *red, int *ctr, unsigned long long *best) {
+  constexpr int EPI = EPI_ == EPI_QKV_F8 ? EPI_QKV : EPI_, PAGES_F8 = EPI_ == EPI_QKV_F8 ? 1 : 0;  // the FP8 form differs in qkv_store only
   const int tid0 = tid_opaque();
   const int wave = __builtin_amdgcn_readfirstlane(tid0 >> 6), lane = tid0 & 63;
   const int K = a.K;
@@ -224,7 +225,7 @@ __device__ __forceinline__ void gemv_phase(const GemvArgs &a, char *smem, float 
         float x, y;
         rope_pair<float>(xs, ys, ax.a[c], ax.b[c], x, y);
         const bool wr0 = single ? own : (own && rr < nvalid && !odd), wr1 = single ? own : (own && rr < nvalid && odd);  // R = 1: one lane writes both
-        if (wr0 || wr1) qkv_store(a.qkv, mi, a.nrows[0], c, slotv[c], dst, x, y, wr0, wr1);
+        if (wr0 || wr1) qkv_store<PAGES_F8>(a.qkv, mi, a.nrows[0], c, slotv[c], dst, x, y, wr0, wr1);
       }
     };
     MRS_DEC_TYPE_SWITCH(jb.mat[0].type, { stream<TT, NCOLS, false, RING2>(jb, K, NCI, mode, smem, ctr, sbar, stage, auxf, epi); })

@@ -302,7 +302,7 @@ template <int EPI> struct Launch {
     for (int i = 0; i < (EPI == EPI_QKV ? 3 : 1); ++i) total_units += a.units[i];
     static const int force_ring2 = [] { const char *e = getenv("MRS_DEC_RING2"); return e ? atoi(e) : -1; }();
     const bool ring2 = force_ring2 >= 0 ? force_ring2 != 0 : total_units >= 8 * grid;
-    return gemv_launch<NCOLS>(EPI, tmask, ring2, grid, lds, a, s);
+    return gemv_launch<NCOLS>(EPI == EPI_QKV && a.qkv.kv_fp8 ? EPI_QKV_F8 : EPI, tmask, ring2, grid, lds, a, s);  // FP8 pages: the kernel's own instantiations
   }
   // activation columns [c0, ...) of a batched launch: every per-column pointer moves
   static GemvArgs shift_cols(GemvArgs a, int c0) {
@@ -363,7 +363,7 @@ extern "C" int mrs_dec_repack(const void *gguf_blocks, int type, long long n, lo
 static int dec_qkv_impl(const mrs_dec_mat_c *wq, const mrs_dec_mat_c *wk, const mrs_dec_mat_c *wv, const float *h, int ldh, const float *norm_w, float eps,
                         float *q_out, void *k_cache, void *v_cache, const int64_t *slot_mapping, const int32_t *positions, const float *cos_t,
                         const float *sin_t, int head_dim, int rot_pairs, int num_kv_heads, int block_size, int kv_dtype, int b, int neox, void *stream,
-                        const void *x_img = nullptr) {
+                        const void *x_img = nullptr, float k_scale = 0.f, float v_scale = 0.f) {
   GemvArgs a{};
   a.neox = neox;
   a.x_img = x_img;
@@ -372,7 +372,8 @@ static int dec_qkv_impl(const mrs_dec_mat_c *wq, const mrs_dec_mat_c *wk, const 
       !make_mat(a.m[2], wv->planes, wv->type, wv->n, wv->k)) return -1;
   if (wq->k != wk->k || wq->k != wv->k) return -1;
   if (act_mode_for(wq->type) != act_mode_for(wk->type) || act_mode_for(wq->type) != act_mode_for(wv->type)) return -1;
-  if (!qkv_epi_fill(a.qkv, q_out, k_cache, v_cache, slot_mapping, positions, cos_t, sin_t, head_dim, rot_pairs, num_kv_heads, block_size, kv_dtype, wq->n, wk->n, wv->n))
+  if (!qkv_epi_fill(a.qkv, q_out, k_cache, v_cache, slot_mapping, positions, cos_t, sin_t, head_dim, rot_pairs, num_kv_heads, block_size, kv_dtype, wq->n, wk->n, wv->n,
+                    k_scale, v_scale))
     return -1;
   a.nrows[0] = (int)wq->n; a.nrows[1] = (int)wk->n; a.nrows[2] = (int)wv->n; a.K = (int)wq->k;
   a.x = h; a.ldx = ldh; a.norm_w = norm_w; a.eps = eps;
@@ -392,6 +393,22 @@ extern "C" int mrs_dec_qkv_neox(const mrs_dec_mat_c *wq, const mrs_dec_mat_c *wk
                                 const float *sin_t, int head_dim, int rot_pairs, int num_kv_heads, int block_size, int kv_dtype, int b, void *stream) {
   return dec_qkv_impl(wq, wk, wv, h, ldh, norm_w, eps, q_out, k_cache, v_cache, slot_mapping, positions, cos_t, sin_t, head_dim, rot_pairs, num_kv_heads, block_size,
                       kv_dtype, b, 1, stream);
+}
+
+// The same launches on FP8 E4M3 pages (K [blocks][kv heads][head_dim / 16][block_size][16], V [blocks][kv heads][head_dim][block_size], one byte per element): the
+// counterpart's arguments with the two static page scales in place of kv_dtype; code = float_to_fp8_e4m3(value / scale).  -1 for a scale that is not finite and > 0.
+extern "C" int mrs_dec_qkv_f8(const mrs_dec_mat_c *wq, const mrs_dec_mat_c *wk, const mrs_dec_mat_c *wv, const float *h, int ldh, const float *norm_w, float eps,
+                              float *q_out, void *k_cache, void *v_cache, const int64_t *slot_mapping, const int32_t *positions, const float *cos_t,
+                              const float *sin_t, int head_dim, int rot_pairs, int num_kv_heads, int block_size, int b, float k_scale, float v_scale, void *stream) {
+  return dec_qkv_impl(wq, wk, wv, h, ldh, norm_w, eps, q_out, k_cache, v_cache, slot_mapping, positions, cos_t, sin_t, head_dim, rot_pairs, num_kv_heads, block_size,
+                      3, b, 0, stream, nullptr, k_scale, v_scale);
+}
+extern "C" int mrs_dec_qkv_neox_f8(const mrs_dec_mat_c *wq, const mrs_dec_mat_c *wk, const mrs_dec_mat_c *wv, const float *h, int ldh, const float *norm_w, float eps,
+                                   float *q_out, void *k_cache, void *v_cache, const int64_t *slot_mapping, const int32_t *positions, const float *cos_t,
+                                   const float *sin_t, int head_dim, int rot_pairs, int num_kv_heads, int block_size, int b, float k_scale, float v_scale,
+                                   void *stream) {
+  return dec_qkv_impl(wq, wk, wv, h, ldh, norm_w, eps, q_out, k_cache, v_cache, slot_mapping, positions, cos_t, sin_t, head_dim, rot_pairs, num_kv_heads, block_size,
+                      3, b, 1, stream, nullptr, k_scale, v_scale);
 }
 
 // gate / up: h -> RMSNorm -> quantize -> act(W_g . x) * (W_u . x) -> act_out f32 [b][ld_out].  expert_sel != nullptr: stacked experts
@@ -480,6 +497,13 @@ extern "C" int mrs_dec_qkv_img(const mrs_dec_mat_c *wq, const mrs_dec_mat_c *wk,
   return dec_qkv_impl(wq, wk, wv, nullptr, 0, nullptr, 0.f, q_out, k_cache, v_cache, slot_mapping, positions, cos_t, sin_t, head_dim, rot_pairs, num_kv_heads, block_size,
                       kv_dtype, b, neox, stream, x_img);
 }
+extern "C" int mrs_dec_qkv_img_f8(const mrs_dec_mat_c *wq, const mrs_dec_mat_c *wk, const mrs_dec_mat_c *wv, const void *x_img, float *q_out, void *k_cache, void *v_cache,
+                                  const int64_t *slot_mapping, const int32_t *positions, const float *cos_t, const float *sin_t, int head_dim, int rot_pairs,
+                                  int num_kv_heads, int block_size, int b, int neox, float k_scale, float v_scale, void *stream) {
+  if (!x_img) return -1;
+  return dec_qkv_impl(wq, wk, wv, nullptr, 0, nullptr, 0.f, q_out, k_cache, v_cache, slot_mapping, positions, cos_t, sin_t, head_dim, rot_pairs, num_kv_heads, block_size,
+                      3, b, neox, stream, x_img, k_scale, v_scale);
+}
 // mrs_dec_gate_up (dense) on an image of RmsNorm(h)
 extern "C" int mrs_dec_gate_up_img(const mrs_dec_mat_c *wg, const mrs_dec_mat_c *wu, int n, const void *x_img, int activation, float *act_out, int ld_out, int b,
                                    void *stream) {
@@ -494,12 +518,12 @@ extern "C" int mrs_dec_gate_up_img(const mrs_dec_mat_c *wg, const mrs_dec_mat_c 
 // img_out: Q8_K activation image for mrs_dec_proj_img (written when the GQA group is even; may be NULL); ticket: [b * num_kv_heads] u32, zero
 // before the first call (the kernel leaves it zero); part_*: the partials workspace of mrs_decode_attention_f32_*.  Returns 1 when the image
 // was written, 0 when only out_f32 was, < 0 on a shape outside the kernel (head size 128, 32-token pages, GQA group 1 / 2 / 4 / 8).
-extern "C" int mrs_dec_attention(float *out_f32, void *img_out, unsigned *ticket, float *part_o, float *part_m, float *part_l, const float *q, const void *k_cache,
-                                 const void *v_cache, int num_kv_heads, float scale, const uint32_t *block_tables, const uint32_t *context_lens, int block_size,
-                                 int max_context_len, int num_seqs, int num_heads, int head_size, int max_blocks_per_seq, int q_stride, int kv_block_stride,
-                                 int kv_head_stride, int kv_dtype, int sliding_window, void *stream) {
+static int dec_attention_impl(float *out_f32, void *img_out, unsigned *ticket, float *part_o, float *part_m, float *part_l, const float *q, const void *k_cache,
+                              const void *v_cache, int num_kv_heads, float scale, const uint32_t *block_tables, const uint32_t *context_lens, int block_size,
+                              int max_context_len, int num_seqs, int num_heads, int head_size, int max_blocks_per_seq, int q_stride, int kv_block_stride,
+                              int kv_head_stride, int kv_dtype /* 0 f16, 1 bf16, 3 fp8 e4m3 */, int sliding_window, float k_scale, float v_scale, void *stream) {
   if (!ticket || !part_o || !part_m || !part_l || block_size != 32 || head_size != 128 || num_seqs <= 0 || num_kv_heads <= 0 || num_heads % num_kv_heads ||
-      (kv_dtype != 0 && kv_dtype != 1) || max_context_len <= 0) return -1;
+      max_context_len <= 0) return -1;
   const int G = num_heads / num_kv_heads;
   if (G != 1 && G != 2 && G != 4 && G != 8) return -1;
   const bool with_img = img_out && (G % 2 == 0) && num_seqs <= 8;
@@ -511,6 +535,7 @@ extern "C" int mrs_dec_attention(float *out_f32, void *img_out, unsigned *ticket
   t.num_heads = num_heads; t.num_kv_heads = num_kv_heads; t.max_blocks_per_seq = max_blocks_per_seq; t.q_stride = q_stride;
   t.kv_block_stride = kv_block_stride; t.kv_head_stride = kv_head_stride; t.num_seqs = num_seqs; t.scale = scale;
   t.window = sliding_window > 0 ? sliding_window : 0;
+  t.k_scale = k_scale; t.v_scale = v_scale;
   const int nblk = (max_context_len + 31) / 32;
   t.bpw = nblk <= 64 ? 1 : (nblk + 63) / 64;                        // == dec_bpw() of paged_attention.hip: at most 64 splits
   t.max_splits = mrs_decode_attention_max_splits(max_context_len);  // stride of the partials, as in mrs_decode_attention_f32_*
@@ -522,10 +547,30 @@ extern "C" int mrs_dec_attention(float *out_f32, void *img_out, unsigned *ticket
   // (write-through partials, drain, device-scope ticket, sc1 loads) costs about what the second launch and its boundary cost -- 472.8 vs 465.4 tok/s for the whole step
 #define MRS_A2(GG, CT) hipLaunchKernelGGL((dec_attn2_kernel<GG, CT>), grid, dim3(64 * GG), 0, s, a)
 #define MRS_A2G(CT) switch (G) { case 1: MRS_A2(1, CT); break; case 2: MRS_A2(2, CT); break; case 4: MRS_A2(4, CT); break; default: MRS_A2(8, CT); break; }
-  if (kv_dtype == 1) { MRS_A2G(bf16_t) } else { MRS_A2G(f16_t) }
+  if (kv_dtype == 3) { MRS_A2G(fp8_t) } else if (kv_dtype == 1) { MRS_A2G(bf16_t) } else { MRS_A2G(f16_t) }
 #undef MRS_A2G
 #undef MRS_A2
   return with_img ? 1 : 0;
+}
+extern "C" int mrs_dec_attention(float *out_f32, void *img_out, unsigned *ticket, float *part_o, float *part_m, float *part_l, const float *q, const void *k_cache,
+                                 const void *v_cache, int num_kv_heads, float scale, const uint32_t *block_tables, const uint32_t *context_lens, int block_size,
+                                 int max_context_len, int num_seqs, int num_heads, int head_size, int max_blocks_per_seq, int q_stride, int kv_block_stride,
+                                 int kv_head_stride, int kv_dtype, int sliding_window, void *stream) {
+  if (kv_dtype != 0 && kv_dtype != 1) return -1;
+  return dec_attention_impl(out_f32, img_out, ticket, part_o, part_m, part_l, q, k_cache, v_cache, num_kv_heads, scale, block_tables, context_lens, block_size,
+                            max_context_len, num_seqs, num_heads, head_size, max_blocks_per_seq, q_stride, kv_block_stride, kv_head_stride, kv_dtype, sliding_window,
+                            1.0f, 1.0f, stream);
+}
+// mrs_dec_attention over FP8 E4M3 pages (the layout of mrs_dec_qkv_f8; strides in elements = bytes): element = f32(fp8_e4m3_to_float(code) * scale), then the same
+// arithmetic in the same order.  The scales go by value: the launch stays graph-capturable without a device read.  -1 for a scale that is not finite and > 0.
+extern "C" int mrs_dec_attention_f8(float *out_f32, void *img_out, unsigned *ticket, float *part_o, float *part_m, float *part_l, const float *q, const void *k_cache,
+                                    const void *v_cache, int num_kv_heads, float scale, const uint32_t *block_tables, const uint32_t *context_lens, int block_size,
+                                    int max_context_len, int num_seqs, int num_heads, int head_size, int max_blocks_per_seq, int q_stride, int kv_block_stride,
+                                    int kv_head_stride, int sliding_window, float k_scale, float v_scale, void *stream) {
+  if (!kv_scale_ok(k_scale) || !kv_scale_ok(v_scale)) return -1;
+  return dec_attention_impl(out_f32, img_out, ticket, part_o, part_m, part_l, q, k_cache, v_cache, num_kv_heads, scale, block_tables, context_lens, block_size,
+                            max_context_len, num_seqs, num_heads, head_size, max_blocks_per_seq, q_stride, kv_block_stride, kv_head_stride, 3, sliding_window,
+                            k_scale, v_scale, stream);
 }
 
 

@@ -551,14 +551,29 @@ extern "C" int mrs_dec_mm_gate_up(const void *qi_gate, const void *qi_up, int ty
   return launch(a, (hipStream_t)stream);
 }
 // q / k / v projections + interleaved RoPE + paged-cache write (mrs_dec_qkv_img's contract, neox = 0 only: a rotate-half pair spans two panels)
-extern "C" int mrs_dec_mm_qkv(const void *qi_q, int type_q, int nq, const void *qi_k, int type_k, int nk, const void *qi_v, int type_v, int nv, int k, const void *x_img,
-                              float *q_out, void *k_cache, void *v_cache, const int64_t *slot_mapping, const int32_t *positions, const float *cos_t, const float *sin_t,
-                              int head_dim, int rot_pairs, int num_kv_heads, int block_size, int kv_dtype, int b, void *stream) {
+static int dec_mm_qkv_impl(const void *qi_q, int type_q, int nq, const void *qi_k, int type_k, int nk, const void *qi_v, int type_v, int nv, int k, const void *x_img,
+                           float *q_out, void *k_cache, void *v_cache, const int64_t *slot_mapping, const int32_t *positions, const float *cos_t, const float *sin_t,
+                           int head_dim, int rot_pairs, int num_kv_heads, int block_size, int kv_dtype, int b, float k_scale, float v_scale, void *stream) {
   MmArgs a{};
   if (!q_out || !k_cache || !v_cache || !slot_mapping || !positions || !cos_t || !sin_t) return -1;
   if (!set_tensor(a.m[0], qi_q, type_q, nq, k) || !set_tensor(a.m[1], qi_k, type_k, nk, k) || !set_tensor(a.m[2], qi_v, type_v, nv, k) || !base(a, x_img, k, b, type_q)) return -1;
-  if (!mrs::dec::qkv_epi_fill(a.qkv, q_out, k_cache, v_cache, slot_mapping, positions, cos_t, sin_t, head_dim, rot_pairs, num_kv_heads, block_size, kv_dtype, nq, nk, nv))
+  if (!mrs::dec::qkv_epi_fill(a.qkv, q_out, k_cache, v_cache, slot_mapping, positions, cos_t, sin_t, head_dim, rot_pairs, num_kv_heads, block_size, kv_dtype, nq, nk, nv,
+                              k_scale, v_scale))
     return -1;
   a.epi = EPI_QKV; a.nseg = 1; a.units = a.m[0].npanels + a.m[1].npanels + a.m[2].npanels;
   return launch(a, (hipStream_t)stream);
+}
+extern "C" int mrs_dec_mm_qkv(const void *qi_q, int type_q, int nq, const void *qi_k, int type_k, int nk, const void *qi_v, int type_v, int nv, int k, const void *x_img,
+                              float *q_out, void *k_cache, void *v_cache, const int64_t *slot_mapping, const int32_t *positions, const float *cos_t, const float *sin_t,
+                              int head_dim, int rot_pairs, int num_kv_heads, int block_size, int kv_dtype, int b, void *stream) {
+  if (kv_dtype != 0 && kv_dtype != 1) return -1;
+  return dec_mm_qkv_impl(qi_q, type_q, nq, qi_k, type_k, nk, qi_v, type_v, nv, k, x_img, q_out, k_cache, v_cache, slot_mapping, positions, cos_t, sin_t, head_dim, rot_pairs,
+                         num_kv_heads, block_size, kv_dtype, b, 0.f, 0.f, stream);
+}
+// the same launch on FP8 E4M3 pages (mrs_dec_qkv_f8's layout and scales)
+extern "C" int mrs_dec_mm_qkv_f8(const void *qi_q, int type_q, int nq, const void *qi_k, int type_k, int nk, const void *qi_v, int type_v, int nv, int k, const void *x_img,
+                                 float *q_out, void *k_cache, void *v_cache, const int64_t *slot_mapping, const int32_t *positions, const float *cos_t, const float *sin_t,
+                                 int head_dim, int rot_pairs, int num_kv_heads, int block_size, int b, float k_scale, float v_scale, void *stream) {
+  return dec_mm_qkv_impl(qi_q, type_q, nq, qi_k, type_k, nk, qi_v, type_v, nv, k, x_img, q_out, k_cache, v_cache, slot_mapping, positions, cos_t, sin_t, head_dim, rot_pairs,
+                         num_kv_heads, block_size, 3, b, k_scale, v_scale, stream);
 }

@@ -889,8 +889,8 @@ __global__ void __launch_bounds__(256) prefill_attn_exact_kernel(const dec::Attn
     constexpr bool WITH_V = decltype(with_v)::value;
     for (int sp = 0; sp < ns_w; ++sp) {
       const int b0 = sp * bpw;
-      int4 kr[8], vr[8];
-      if (ONE) dec::attn_load_block<WITH_V>(a, base_of(b0), kr, vr);
+      int4 kr[dec::AttnRegs<CT>::NK], vr[dec::AttnRegs<CT>::NV];
+      if (ONE) dec::attn_load_block<CT, WITH_V>(a, base_of(b0), kr, vr);
       for (int i = 0; i < nq; ++i) {
         const int ctx = (int)a.context_lens[t0 + i], nblk = (ctx + 31) / 32;
         if (sp >= (nblk + bpw - 1) / bpw) continue;  // this token's decode step has no such split
@@ -900,7 +900,7 @@ __global__ void __launch_bounds__(256) prefill_attn_exact_kernel(const dec::Attn
         for (int g = 0; g < G; ++g) { m[g] = -FLT_MAX; l[g] = 0.f; o0[g] = 0.f; o1[g] = 0.f; }
         if (b1 * 32 > lo) {  // else: the split lies before the sliding window -- what a fully masked pass gives (mrs_dec_attention publishes the same)
           for (int b = b0; b < b1; ++b) {
-            if (!ONE) dec::attn_load_block<WITH_V>(a, base_of(b), kr, vr);
+            if (!ONE) dec::attn_load_block<CT, WITH_V>(a, base_of(b), kr, vr);
             dec::attn_block_update<G, CT, WITH_V>(a, kr, vr, q_s + (size_t)i * G * HD, p_s, b, b == b0, ctx, lo, m, l, o0, o1);
           }
         }
@@ -965,6 +965,21 @@ template <> __device__ __forceinline__ float cvt16_lo<bf16_t>(unsigned w) { retu
 template <> __device__ __forceinline__ float cvt16_hi<bf16_t>(unsigned w) { return __uint_as_float(w & 0xffff0000u); }
 template <> __device__ __forceinline__ float cvt16_lo<f16_t>(unsigned w) { return half_bits_to_float((uint16_t)(w & 0xffffu)); }
 template <> __device__ __forceinline__ float cvt16_hi<f16_t>(unsigned w) { return half_bits_to_float((uint16_t)(w >> 16)); }
+// Element 2 u + kp of a 16-byte chunk as f32: the MFMA step u of the chunk takes the even (kp = 0) or odd element of its pair.  16-bit pages: 8 elements = 4 steps
+// per chunk; FP8 pages: 16 codes = 8 steps, element = f32(fp8_e4m3_to_float(code) * scale) (dec_attn.cuh).
+template <class CT> struct PmChunk { static constexpr bool F8 = is_fp8<CT>::value; static constexpr int STEPS = F8 ? 8 : 4; };
+template <class CT> __device__ __forceinline__ float pm_elem(const unsigned (&w4)[4], int u, int kp, float scale) {
+  if constexpr (PmChunk<CT>::F8) {
+    const unsigned code = (w4[u >> 1] >> (16 * (u & 1) + 8 * kp)) & 0xffu;
+#if defined(__gfx950__) && !defined(MRS_FP8_INTEGER_DECODE)
+    return __builtin_amdgcn_cvt_f32_fp8((int)code, 0) * scale;
+#else
+    return fp8_e4m3_to_float((uint8_t)code) * scale;
+#endif
+  } else {
+    return kp ? cvt16_hi<CT>(w4[u]) : cvt16_lo<CT>(w4[u]);
+  }
+}
 #ifndef MRS_MFMA_F32_K1_FIRST
 #define MRS_MFMA_F32_K1_FIRST 0  // 1: the instruction adds k = 1 before k = 0 (then the lane halves swap dims / tokens); the probe says 0 on gfx950
 #endif
@@ -1013,31 +1028,33 @@ __global__ void __launch_bounds__(64 * PM_NW, 2) prefill_attn_mfma_kernel(const 
   f16v zero;
 #pragma unroll
   for (int v = 0; v < 16; ++v) zero[v] = 0.f;
-  // K of a block as the A operand of the score MFMAs: lane (token j, half) supplies K[token j][2 s + kp]; chunk c = dims 8 c .. 8 c + 7 (16 bytes).  The 16 chunk
+  // K of a block as the A operand of the score MFMAs: lane (token j, half) supplies K[token j][2 s + kp]; chunk c = dims 8 c .. 8 c + 7 (16 bytes; FP8 pages: dims
+  // 16 c .. 16 c + 15, so 8 chunks).  Either way a token's chunk is 16 bytes and consecutive chunks lie 32 x 16 bytes apart.  The chunk
   // registers are a ring in place: chunk c of the NEXT block the wave will score is requested as soon as chunk c of the current one has been converted (a block's
   // loads used to sit exposed in front of its MFMAs; a second register set costs the occupancy: 220 + 48 registers)
-  auto k_ptr = [&](int b) { return a.k_cache + (size_t)bt[b] * a.kv_block_stride + (size_t)kvh * a.kv_head_stride + (size_t)j * 8; };
-  auto load_k = [&](int b, v4u (&kr)[16]) {
-    const uint16_t *kb = k_ptr(b);
+  constexpr int ES = (int)sizeof(CT), SPC = PmChunk<CT>::STEPS, NKC = 64 / SPC, NVC = 16 / SPC;  // bytes per element; MFMA steps per chunk; K chunks per token; V chunks per row
+  auto k_ptr = [&](int b) { return (const char *)a.k_cache + ((size_t)bt[b] * a.kv_block_stride + (size_t)kvh * a.kv_head_stride) * ES + (size_t)j * 16; };
+  auto load_k = [&](int b, v4u (&kr)[NKC]) {
+    const char *kb = k_ptr(b);
 #pragma unroll
-    for (int c = 0; c < 16; ++c) kr[c] = *(const v4u *)(kb + (size_t)c * 32 * 8);
+    for (int c = 0; c < NKC; ++c) kr[c] = *(const v4u *)(kb + (size_t)c * 32 * 16);
   };
   // scores of block b for the 32 queries: lane (query j, half hf) gets tokens i = 8 (v / 4) + 4 hf + v % 4 (the accumulator layout); masked + scaled; returns the block max.
   // b_next: the block whose K replaces the registers (b itself when there is none: the reload is then unused, the code stays straight-line)
-  auto scores = [&](v4u (&kr)[16], int b, int b_next, float (&val)[16], bool (&ok)[16]) -> float {
-    const uint16_t *kn = k_ptr(b_next);
+  auto scores = [&](v4u (&kr)[NKC], int b, int b_next, float (&val)[16], bool (&ok)[16]) -> float {
+    const char *kn = k_ptr(b_next);
     f16v acc0 = zero, acc1 = zero;
 #pragma unroll
-    for (int c = 0; c < 16; ++c) {
+    for (int c = 0; c < NKC; ++c) {
       const unsigned w4[4] = {kr[c].x, kr[c].y, kr[c].z, kr[c].w};
-      float kv[4];
+      float kv[SPC];
 #pragma unroll
-      for (int u = 0; u < 4; ++u) kv[u] = kp ? cvt16_hi<CT>(w4[u]) : cvt16_lo<CT>(w4[u]);
-      kr[c] = *(const v4u *)(kn + (size_t)c * 32 * 8);
+      for (int u = 0; u < SPC; ++u) kv[u] = pm_elem<CT>(w4, u, kp, a.k_scale);
+      kr[c] = *(const v4u *)(kn + (size_t)c * 32 * 16);
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const float qv = q_s[(c * 4 + u) * 64 + lane];
-        if (c < 8) acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(kv[u], qv, acc0, 0, 0, 0);
+      for (int u = 0; u < SPC; ++u) {
+        const float qv = q_s[(c * SPC + u) * 64 + lane];
+        if (c < NKC / 2) acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(kv[u], qv, acc0, 0, 0, 0);
         else acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(kv[u], qv, acc1, 0, 0, 0);
       }
     }
@@ -1052,7 +1069,7 @@ __global__ void __launch_bounds__(64 * PM_NW, 2) prefill_attn_mfma_kernel(const 
     }
     return fmaxf(mx, __shfl_xor(mx, 32, 64));
   };
-  v4u kcur[16];
+  v4u kcur[NKC];
   // ---- pass A: block maxima (wave w: blocks w, w + 4, ...); its last call reloads the wave's first block for pass B
   if (wave < nblk) load_k(wave, kcur);
   for (int b = wave; b < nblk; b += PM_NW) {
@@ -1068,14 +1085,14 @@ __global__ void __launch_bounds__(64 * PM_NW, 2) prefill_attn_mfma_kernel(const 
   f16v acc = zero, osp = zero;  // merge accumulator and the current split's running output: dims 32 wave + 8 (v / 4) + 4 hf + v % 4 of query j
   float s_all = 0.f, l_run = 0.f;
   // V of block b, dims 32 wave .. + 31, as the A operand of the P . V MFMAs: lane (dim row, half) supplies V[dim][token 2 s + kp] = dword s of the dim's 32-token row
-  auto load_v = [&](int b, v4u (&vr)[4]) {
+  auto load_v = [&](int b, v4u (&vr)[NVC]) {
     const size_t base = (size_t)bt[b] * a.kv_block_stride + (size_t)kvh * a.kv_head_stride;
-    const uint16_t *vb = a.v_cache + base + (size_t)(32 * wave + j) * 32;
+    const char *vb = (const char *)a.v_cache + (base + (size_t)(32 * wave + j) * 32) * ES;
 #pragma unroll
-    for (int c = 0; c < 4; ++c) vr[c] = *(const v4u *)(vb + c * 8);
+    for (int c = 0; c < NVC; ++c) vr[c] = *(const v4u *)(vb + c * 16);
   };
   for (int g0 = 0; g0 < nblk; g0 += PM_NW) {
-    v4u vcur[4], vnext[4];
+    v4u vcur[NVC], vnext[NVC];
     load_v(g0, vcur);  // phase 2's first block: in flight during phase 1
     {  // phase 1
       const int b = g0 + wave;
@@ -1127,12 +1144,12 @@ __global__ void __launch_bounds__(64 * PM_NW, 2) prefill_attn_mfma_kernel(const 
         }
         const float *pr = p_s + (size_t)sl * 1024;
 #pragma unroll
-        for (int c = 0; c < 4; ++c) {
+        for (int c = 0; c < NVC; ++c) {
           const unsigned w4[4] = {vcur[c].x, vcur[c].y, vcur[c].z, vcur[c].w};
 #pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            const int s = 4 * c + u, tok = 2 * s + kp;
-            float vv = kp ? cvt16_hi<CT>(w4[u]) : cvt16_lo<CT>(w4[u]);
+          for (int u = 0; u < SPC; ++u) {
+            const int s = SPC * c + u, tok = 2 * s + kp;
+            float vv = pm_elem<CT>(w4, u, kp, a.v_scale);
             vv = b * 32 + tok < ctx_max ? vv : 0.f;  // slots past the tile's longest context may hold anything (the decode kernel zeroes past ITS context: those p are 0)
             o = __builtin_amdgcn_mfma_f32_32x32x2f32(vv, pr[tok * 32 + j], o, 0, 0, 0);
           }
@@ -1145,7 +1162,7 @@ __global__ void __launch_bounds__(64 * PM_NW, 2) prefill_attn_mfma_kernel(const 
           for (int v = 0; v < 16; ++v) { const float t0 = o[v] * wsp; acc[v] = acc[v] + t0; }
         }
 #pragma unroll
-        for (int c = 0; c < 4; ++c) vcur[c] = vnext[c];
+        for (int c = 0; c < NVC; ++c) vcur[c] = vnext[c];
       }
     }
     __syncthreads();
@@ -1163,16 +1180,18 @@ __global__ void __launch_bounds__(64 * PM_NW, 2) prefill_attn_mfma_kernel(const 
 
 // q f32 [T][q_stride] (RoPE applied), pages already hold the prompt's K / V; context_lens [T] = position + 1 of every prompt token (device), block_table = the
 // sequence's row; out f32 [T][num_heads * 128].  max_context_len = the model's (it fixes the split length exactly as in mrs_dec_attention).
-extern "C" int mrs_prefill_attention_exact(const float *q, const void *k_cache, const void *v_cache, const uint32_t *block_table, const uint32_t *context_lens, float *out,
-                                           int T, int num_heads, int num_kv_heads, int head_size, int block_size, int q_stride, int kv_block_stride, int kv_head_stride,
-                                           float scale, int max_context_len, int kv_dtype, int sliding_window, int max_prompt_ctx, void *stream) {
-  if (!q || !out || head_size != 128 || block_size != 32 || T <= 0 || num_kv_heads <= 0 || num_heads % num_kv_heads || (kv_dtype != 0 && kv_dtype != 1)) return -1;
+static int prefill_attention_exact_impl(const float *q, const void *k_cache, const void *v_cache, const uint32_t *block_table, const uint32_t *context_lens, float *out,
+                                        int T, int num_heads, int num_kv_heads, int head_size, int block_size, int q_stride, int kv_block_stride, int kv_head_stride,
+                                        float scale, int max_context_len, int kv_dtype /* 0 f16, 1 bf16, 3 fp8 e4m3 */, int sliding_window, int max_prompt_ctx, float k_scale,
+                                        float v_scale, void *stream) {
+  if (!q || !out || head_size != 128 || block_size != 32 || T <= 0 || num_kv_heads <= 0 || num_heads % num_kv_heads) return -1;
   const int G = num_heads / num_kv_heads;
   if (G != 1 && G != 2 && G != 4 && G != 8) return -1;
   mrs::dec::AttnArgs a{};
   a.q = q; a.k_cache = (const uint16_t *)k_cache; a.v_cache = (const uint16_t *)v_cache; a.block_tables = block_table; a.context_lens = context_lens;
   a.out = out; a.num_heads = num_heads; a.num_kv_heads = num_kv_heads; a.max_blocks_per_seq = 0 /* every token reads the same row */; a.q_stride = q_stride;
   a.kv_block_stride = kv_block_stride; a.kv_head_stride = kv_head_stride; a.num_seqs = T; a.scale = scale; a.window = sliding_window > 0 ? sliding_window : 0;
+  a.k_scale = k_scale; a.v_scale = v_scale;
   const int nblk = (max_context_len + 31) / 32;
   a.bpw = nblk <= 64 ? 1 : (nblk + 63) / 64;  // == mrs_dec_attention
   // (w_j, l_j) per split live in LDS: as many splits as the longest context of this prompt needs (<= 64 by the rule above)
@@ -1184,7 +1203,8 @@ extern "C" int mrs_prefill_attention_exact(const float *q, const void *k_cache, 
     const size_t lds_m = (size_t)mrs::qi::PM_Q + mrs::qi::PM_P + mrs::qi::PM_SC + (size_t)nb * 128;
     if (lds_m <= mrs::LDS_DYN_MAX) {
       const dim3 gm(num_heads, (T + 31) / 32);
-      if (kv_dtype == 1) { auto kern = mrs::qi::prefill_attn_mfma_kernel<mrs::bf16_t>; mrs::lds_attr_once((const void *)kern, mrs::LDS_DYN_MAX); hipLaunchKernelGGL(kern, gm, dim3(64 * mrs::qi::PM_NW), lds_m, (hipStream_t)stream, a, nb); }
+      if (kv_dtype == 3) { auto kern = mrs::qi::prefill_attn_mfma_kernel<mrs::fp8_t>; mrs::lds_attr_once((const void *)kern, mrs::LDS_DYN_MAX); hipLaunchKernelGGL(kern, gm, dim3(64 * mrs::qi::PM_NW), lds_m, (hipStream_t)stream, a, nb); }
+      else if (kv_dtype == 1) { auto kern = mrs::qi::prefill_attn_mfma_kernel<mrs::bf16_t>; mrs::lds_attr_once((const void *)kern, mrs::LDS_DYN_MAX); hipLaunchKernelGGL(kern, gm, dim3(64 * mrs::qi::PM_NW), lds_m, (hipStream_t)stream, a, nb); }
       else { auto kern = mrs::qi::prefill_attn_mfma_kernel<mrs::f16_t>; mrs::lds_attr_once((const void *)kern, mrs::LDS_DYN_MAX); hipLaunchKernelGGL(kern, gm, dim3(64 * mrs::qi::PM_NW), lds_m, (hipStream_t)stream, a, nb); }
       return 0;
     }
@@ -1199,8 +1219,23 @@ extern "C" int mrs_prefill_attention_exact(const float *q, const void *k_cache, 
 #define MRS_PA(GG, CT) { if (a.bpw == 1) { auto kern = mrs::qi::prefill_attn_exact_kernel<GG, CT, true>; mrs::lds_attr_once((const void *)kern, mrs::LDS_DYN_MAX); hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, a, qw); } \
                          else { auto kern = mrs::qi::prefill_attn_exact_kernel<GG, CT, false>; mrs::lds_attr_once((const void *)kern, mrs::LDS_DYN_MAX); hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, a, qw); } }
 #define MRS_PAG(CT) switch (G) { case 1: MRS_PA(1, CT) break; case 2: MRS_PA(2, CT) break; case 4: MRS_PA(4, CT) break; default: MRS_PA(8, CT) break; }
-  if (kv_dtype == 1) { MRS_PAG(mrs::bf16_t) } else { MRS_PAG(mrs::f16_t) }
+  if (kv_dtype == 3) { MRS_PAG(mrs::fp8_t) } else if (kv_dtype == 1) { MRS_PAG(mrs::bf16_t) } else { MRS_PAG(mrs::f16_t) }
 #undef MRS_PAG
 #undef MRS_PA
   return 0;
+}
+extern "C" int mrs_prefill_attention_exact(const float *q, const void *k_cache, const void *v_cache, const uint32_t *block_table, const uint32_t *context_lens, float *out,
+                                           int T, int num_heads, int num_kv_heads, int head_size, int block_size, int q_stride, int kv_block_stride, int kv_head_stride,
+                                           float scale, int max_context_len, int kv_dtype, int sliding_window, int max_prompt_ctx, void *stream) {
+  if (kv_dtype != 0 && kv_dtype != 1) return -1;
+  return prefill_attention_exact_impl(q, k_cache, v_cache, block_table, context_lens, out, T, num_heads, num_kv_heads, head_size, block_size, q_stride, kv_block_stride,
+                                      kv_head_stride, scale, max_context_len, kv_dtype, sliding_window, max_prompt_ctx, 1.0f, 1.0f, stream);
+}
+// the same over FP8 E4M3 pages (mrs_dec_attention_f8's layout, scales and arithmetic: row t equals that launch at context_lens[t] bit for bit)
+extern "C" int mrs_prefill_attention_exact_f8(const float *q, const void *k_cache, const void *v_cache, const uint32_t *block_table, const uint32_t *context_lens, float *out,
+                                              int T, int num_heads, int num_kv_heads, int head_size, int block_size, int q_stride, int kv_block_stride, int kv_head_stride,
+                                              float scale, int max_context_len, int sliding_window, int max_prompt_ctx, float k_scale, float v_scale, void *stream) {
+  if (!mrs::dec::kv_scale_ok(k_scale) || !mrs::dec::kv_scale_ok(v_scale)) return -1;
+  return prefill_attention_exact_impl(q, k_cache, v_cache, block_table, context_lens, out, T, num_heads, num_kv_heads, head_size, block_size, q_stride, kv_block_stride,
+                                      kv_head_stride, scale, max_context_len, 3, sliding_window, max_prompt_ctx, k_scale, v_scale, stream);
 }

@@ -176,6 +176,9 @@ struct Block {
   QTensor gate_exps, up_exps, down_exps;
   const float *input_layernorm = nullptr, *post_attention_layernorm = nullptr;
   void *key_cache = nullptr, *value_cache = nullptr;
+  // FP8 pages: the layer's static scales -- by value for the engine's launches, as two device floats (carved from the decode workspace) for reshape_and_cache
+  float k_scale = 1.0f, v_scale = 1.0f;
+  float *kv_scales_dev = nullptr;
   // the seven dense linears in the fixed order q, k, v, o, gate, up, down (a MoE block has the first four only)
   std::array<const GgufMatMul *, 7> dense() const { return {q_proj.get(), k_proj.get(), v_proj.get(), o_proj.get(), gate_proj.get(), up_proj.get(), down_proj.get()}; }
 };
@@ -205,6 +208,7 @@ struct Workspace {  // carve-up of the caller's scratch
   void *moe_router_scratch; // [B][experts + 1]: logits + arrival ticket of the split router (mrs_moe_router_topk_norm_split; zero at rest)
   void *attn_img;           // decode engine: Q8_K activation image of the attention result (mrs_dec_attention / mrs_dec_attention_q8k -> mrs_dec_proj_img)
   unsigned *attn_ticket;    // decode engine: [max_batch][kv heads] arrival counters of mrs_dec_attention (zero at rest)
+  float *kv_scales;         // FP8 pages: [layers][2] the static k / v scales as device floats (reshape_and_cache reads them on the device)
   void *act_img;            // decode engine, batched steps: the activation image of a phase, built once (mrs_dec_act_image -> mrs_dec_*_img); hidden or ffn width, <= 8 columns
 };
 
@@ -259,6 +263,7 @@ class Llama {
       w.moe_act = a.take<float>(k * ff * 4);
       w.moe_router_scratch = a.take(mrs_moe_router_split_scratch_bytes((int)B, (int)c.num_experts));
     }
+    w.kv_scales = a.take<float>((size_t)c.num_layers * 2 * 4);
     return a.off;
   }
   static size_t workspace_bytes(const mrs_llama_config &c) { Workspace w{}; return lay_out(c, nullptr, w) + WORKSPACE_SLACK; }
@@ -270,7 +275,27 @@ class Llama {
     // zero once: Q8_1 padding blocks beyond K are never written by the fused epilogues; sample scratch must start at 0
     if (hipMemset(b.workspace, 0, b.workspace_bytes) != hipSuccess) return fail("hipMemset(workspace) failed");
     have_bufs = true;
+    for (size_t i = 0; i < blocks.size(); ++i)
+      if (upload_kv_scales((int)i)) return -1;
     return 0;
+  }
+  // ---- page dtype: cfg.kv_f16 is a code (0 bf16, 1 f16, 2 FP8 E4M3 with per-layer static scales)
+  bool kv_fp8() const { return cfg.kv_f16 == 2; }
+  int engine_kv_dtype() const { return cfg.kv_f16 == 2 ? 3 : cfg.kv_f16 == 1 ? 0 : 1; }  // the kernels' code: 1 bf16, 0 f16, 3 fp8
+  int upload_kv_scales(int layer) {
+    Block &bl = blocks[layer];
+    bl.kv_scales_dev = ws.kv_scales + 2 * (size_t)layer;
+    const float two[2] = {bl.k_scale, bl.v_scale};
+    return hipMemcpy(bl.kv_scales_dev, two, sizeof(two), hipMemcpyHostToDevice) == hipSuccess ? 0 : fail("hipMemcpy(kv scales) failed");
+  }
+  // The device copy is written with a blocking hipMemcpy: the caller must have synchronised every stream on which a prompt (reshape_and_cache reads these floats) may
+  // still run -- Llama.set_kv_scales (llama.py) synchronises the device first.  Decode launches take the scales by value and never read the copy.
+  int set_kv_scales(int layer, float k, float v) {
+    if (layer < 0 || layer >= (int)blocks.size()) return fail("mrs_llama_set_kv_scales: layer %d out of range", layer);
+    if (!kv_fp8()) return fail("mrs_llama_set_kv_scales: the model has no FP8 KV pages");
+    if (!(k > 0.f && k < INFINITY && v > 0.f && v < INFINITY)) return fail("mrs_llama_set_kv_scales: scales must be finite and > 0 (got %g, %g)", (double)k, (double)v);
+    blocks[layer].k_scale = k; blocks[layer].v_scale = v;
+    return have_bufs ? upload_kv_scales(layer) : 0;
   }
 
   int check_ready(int b) const {
@@ -306,10 +331,10 @@ class Llama {
   }
 
   // what every attention launch (decode and prompt) takes from the config
-  struct AttnGeom { int eff_max; float scale; int block_stride, head_stride, kvd; };  // longest context of a block table; 1 / sqrt(head_dim); elements per page / per KV head of a page; engine page dtype (1 bf16, 0 f16)
+  struct AttnGeom { int eff_max; float scale; int block_stride, head_stride, kvd; };  // longest context of a block table; 1 / sqrt(head_dim); elements per page / per KV head of a page; engine page dtype (1 bf16, 0 f16, 3 fp8)
   AttnGeom attn_geom() const {
     const int hd = cfg.head_dim, bs = cfg.block_size;
-    return AttnGeom{std::min(cfg.max_blocks_per_seq * bs, cfg.max_context_len), 1.0f / sqrtf((float)hd), cfg.num_kv_heads * hd * bs, hd * bs, cfg.kv_f16 ? 0 : 1};
+    return AttnGeom{std::min(cfg.max_blocks_per_seq * bs, cfg.max_context_len), 1.0f / sqrtf((float)hd), cfg.num_kv_heads * hd * bs, hd * bs, engine_kv_dtype()};
   }
 
   // PagedAttention::forward, decode branch (run_decode): attention over the cache that already holds this token
@@ -462,11 +487,23 @@ class Llama {
   // RmsNorm(h) -> q (f32, RoPE applied) + k / v into the layer's pages.  The matrix cores only when all three tensors qualify and RoPE is interleaved (a rotate-half pair
   // spans two panels); rotate-half: the caller registered q / k decode planes in pair order (mrs_dec_qkv_neox; llama.py permutes the rows before the repack)
   int qkv_phase(const Block &bl, int b, hipStream_t s) const {
-    const int d = cfg.hidden_size, hd = cfg.head_dim, rp = cfg.rot_dim / 2, kvh = cfg.num_kv_heads, bs = cfg.block_size, kvd = cfg.kv_f16 ? 0 : 1;
+    const int d = cfg.hidden_size, hd = cfg.head_dim, rp = cfg.rot_dim / 2, kvh = cfg.num_kv_heads, bs = cfg.block_size, kvd = engine_kv_dtype();
     const Lin q = lin(bl.dq, bl.q_proj, d), k = lin(bl.dk, bl.k_proj, d), v = lin(bl.dv, bl.v_proj, d);
     Route r = std::min(route(q, b), std::min(route(k, b), route(v, b)));
     if (r == R_IMG_MM && !cfg.rope_interleaved) r = R_IMG_VALU;
     if (r != R_INLINE && act_image(ws.h, bl.input_layernorm, q, b, s)) return -1;
+    if (kv_fp8()) {  // the same three launches on FP8 pages: the layer's scales by value
+      const float ks = bl.k_scale, vs = bl.v_scale;
+      switch (r) {
+      case R_INLINE: return (cfg.rope_interleaved ? mrs_dec_qkv_f8 : mrs_dec_qkv_neox_f8)(q.mat, k.mat, v.mat, ws.h, d, bl.input_layernorm, cfg.rms_eps, ws.q, bl.key_cache,
+                                                                                        bl.value_cache, bufs.slot_mapping, bufs.positions, bufs.cos_table, bufs.sin_table, hd, rp,
+                                                                                        kvh, bs, b, ks, vs, s);
+      case R_IMG_VALU: return mrs_dec_qkv_img_f8(q.mat, k.mat, v.mat, ws.act_img, ws.q, bl.key_cache, bl.value_cache, bufs.slot_mapping, bufs.positions, bufs.cos_table,
+                                               bufs.sin_table, hd, rp, kvh, bs, b, cfg.rope_interleaved ? 0 : 1, ks, vs, s);
+      default: return mrs_dec_mm_qkv_f8(q.qi, q.mat->type, (int)q.mat->n, k.qi, k.mat->type, (int)k.mat->n, v.qi, v.mat->type, (int)v.mat->n, d, ws.act_img, ws.q, bl.key_cache,
+                                        bl.value_cache, bufs.slot_mapping, bufs.positions, bufs.cos_table, bufs.sin_table, hd, rp, kvh, bs, b, ks, vs, s);
+      }
+    }
     switch (r) {
     case R_INLINE: return (cfg.rope_interleaved ? mrs_dec_qkv : mrs_dec_qkv_neox)(q.mat, k.mat, v.mat, ws.h, d, bl.input_layernorm, cfg.rms_eps, ws.q, bl.key_cache, bl.value_cache,
                                                                               bufs.slot_mapping, bufs.positions, bufs.cos_table, bufs.sin_table, hd, rp, kvh, bs, kvd, b, s);
@@ -516,9 +553,13 @@ class Llama {
       if (qkv_phase(bl, b, s)) return fail("q / k / v phase refused the layer");
       // one launch: splits + last-arriver merge; even GQA groups hand o_proj the Q8_K image of the result (Q8_0 weights take Q8_0 activations: f32 result)
       const bool want_img = bl.dout.type != 8 && (cfg.num_heads / kvh) % 2 == 0 && mrs_dec_act_image_bytes(nq, b) <= mrs_dec_proj_img_max_bytes();
-      const int rc2 = mrs_dec_attention(want_img ? nullptr : ws.attn, want_img ? ws.attn_img : nullptr, ws.attn_ticket, (float *)ws.attn_ws, ws.max_logits, ws.exp_sums, ws.q,
-                                        bl.key_cache, bl.value_cache, kvh, ag.scale, bufs.block_tables, bufs.context_lens, bs, ag.eff_max, b, cfg.num_heads, hd,
-                                        cfg.max_blocks_per_seq, nq, ag.block_stride, ag.head_stride, ag.kvd, cfg.sliding_window, s);
+      const int rc2 = kv_fp8()
+          ? mrs_dec_attention_f8(want_img ? nullptr : ws.attn, want_img ? ws.attn_img : nullptr, ws.attn_ticket, (float *)ws.attn_ws, ws.max_logits, ws.exp_sums, ws.q,
+                                 bl.key_cache, bl.value_cache, kvh, ag.scale, bufs.block_tables, bufs.context_lens, bs, ag.eff_max, b, cfg.num_heads, hd,
+                                 cfg.max_blocks_per_seq, nq, ag.block_stride, ag.head_stride, cfg.sliding_window, bl.k_scale, bl.v_scale, s)
+          : mrs_dec_attention(want_img ? nullptr : ws.attn, want_img ? ws.attn_img : nullptr, ws.attn_ticket, (float *)ws.attn_ws, ws.max_logits, ws.exp_sums, ws.q,
+                              bl.key_cache, bl.value_cache, kvh, ag.scale, bufs.block_tables, bufs.context_lens, bs, ag.eff_max, b, cfg.num_heads, hd,
+                              cfg.max_blocks_per_seq, nq, ag.block_stride, ag.head_stride, ag.kvd, cfg.sliding_window, s);
       if (rc2 < 0) return fail("mrs_dec_attention refused the shape");
       // TP: h <- h / world + W_o . attn on every rank, then ONE sum all-reduce of h (the residual add stays fused, as in forward_fused).  An f32 attention result (odd GQA
       // groups, Q8_0 o_proj) is quantized inside the GEMV at every batch size.
@@ -622,12 +663,13 @@ class Llama {
   static size_t prefill_workspace_bytes(const mrs_llama_config &c, int T) { PrefillBufs P; return lay_out_prefill(c, T, nullptr, P) + WORKSPACE_SLACK; }
 
   // ---- layer steps the prompt paths share
-  // rotary on q / k rows of the given strides, then k / v into the layer's pages (cache_kind: reshape_and_cache's page dtype selector)
+  // rotary on q / k rows of the given strides, then k / v into the layer's pages (cache_kind: reshape_and_cache's page dtype selector; 3 = FP8 bytes, 16 dims per K
+  // group, the layer's scales read from the device -- the byte the decode epilogue stores for the same f32 value)
   void rope_and_cache(const Block &bl, float *q, float *k, float *v, int q_stride, int kv_stride, int cache_kind, const mrs_llama_prefill_args &pa, int T, hipStream_t s) const {
     rotary_embedding_positions(q, k, (void *)bufs.cos_table, (void *)bufs.sin_table, (void *)pa.positions, cfg.rope_interleaved ? 0 : 1, cfg.head_dim, T,
                                cfg.rot_dim / 2, cfg.max_context_len, cfg.num_heads, cfg.num_kv_heads, q_stride, kv_stride, 2, (int64_t)(intptr_t)s);
-    reshape_and_cache(k, v, bl.key_cache, bl.value_cache, (int64_t *)pa.slot_mapping, T, cfg.num_kv_heads, cfg.head_dim, cfg.block_size, 8, kv_stride, kv_stride, s, 2, cache_kind,
-                      nullptr, nullptr);
+    reshape_and_cache(k, v, bl.key_cache, bl.value_cache, (int64_t *)pa.slot_mapping, T, cfg.num_kv_heads, cfg.head_dim, cfg.block_size, cache_kind == 3 ? 16 : 8, kv_stride, kv_stride, s, 2,
+                      cache_kind, cache_kind == 3 ? bl.kv_scales_dev : nullptr, cache_kind == 3 ? bl.kv_scales_dev + 1 : nullptr);
   }
   // o_proj / down_proj of the bf16 paths, gemm(out, accumulate): h += W . x; row-parallel shards: partial into xn -> all-reduce -> residual add (bias-free)
   template <class Gemm> int residual_gemm(Gemm &&gemm, const PrefillBufs &P, int T, hipStream_t s) const {
@@ -792,9 +834,12 @@ class Llama {
     if (wte->embedding_forward_raw(pa.token_ids, T, h, s)) return -1;
     for (const Block &bl : blocks) {
       if (group({{bl.q_proj.get(), nq, P.q}, {bl.k_proj.get(), nkv, P.k}, {bl.v_proj.get(), nkv, P.v}}, bl.input_layernorm)) return -1;
-      rope_and_cache(bl, P.q, P.k, P.v, nq, nkv, ag.kvd == 1 ? 1 : 0, pa, T, s);
-      if (mrs_prefill_attention_exact(P.q, bl.key_cache, bl.value_cache, pa.block_tables, pa.context_lens, P.attn, T, cfg.num_heads, cfg.num_kv_heads, hd, cfg.block_size, nq,
-                                      ag.block_stride, ag.head_stride, ag.scale, ag.eff_max, ag.kvd, cfg.sliding_window, pa.start_pos + T, s))
+      rope_and_cache(bl, P.q, P.k, P.v, nq, nkv, ag.kvd, pa, T, s);  // (the engine's page dtype codes are reshape_and_cache's)
+      if (kv_fp8() ? mrs_prefill_attention_exact_f8(P.q, bl.key_cache, bl.value_cache, pa.block_tables, pa.context_lens, P.attn, T, cfg.num_heads, cfg.num_kv_heads, hd,
+                                                    cfg.block_size, nq, ag.block_stride, ag.head_stride, ag.scale, ag.eff_max, cfg.sliding_window, pa.start_pos + T, bl.k_scale,
+                                                    bl.v_scale, s)
+                   : mrs_prefill_attention_exact(P.q, bl.key_cache, bl.value_cache, pa.block_tables, pa.context_lens, P.attn, T, cfg.num_heads, cfg.num_kv_heads, hd,
+                                                 cfg.block_size, nq, ag.block_stride, ag.head_stride, ag.scale, ag.eff_max, ag.kvd, cfg.sliding_window, pa.start_pos + T, s))
         return fail("prefill (exact): attention refused the shape");
       if (row_parallel(*bl.o_proj, d, nq, P.attn, nullptr, nq, nullptr)) return -1;
       if (cfg.num_experts > 0) {
@@ -951,7 +996,9 @@ class Llama {
     if (!wte || !lm_head || !ln_f) return fail("model is missing token_embd / output / output_norm");
     PrefillBufs P;
     if (pa.workspace_bytes < lay_out_prefill(cfg, T, pa.workspace, P) + WORKSPACE_SLACK) return fail("prefill workspace too small");
+    if (kv_fp8() && !have_bufs) return fail("prefill: FP8 KV pages need mrs_llama_set_buffers first (the page scales live in the decode workspace)");
     if (prefill_exact_ok()) return prefill_exact(P, pa, T, s);
+    if (kv_fp8()) return fail("prefill: FP8 KV pages need the exact prompt path (decode engine, prefill mode 1): the bf16 prompt paths read and write bf16 pages");
     return shadow_selected(T) ? prefill_shadow(P, pa, T, s) : prefill_dequant(P, pa, T, s);
   }
   double prefill_flops(int T) const {
@@ -971,6 +1018,7 @@ class Llama {
     if (check_ready(b)) return -1;
     // sliding-window attention (Mistral) exists in the decode engine's split attention and in the MFMA prefill only: every other path would silently attend everything
     if (cfg.sliding_window > 0 && cfg.use_fused != 2) return fail("sliding_window %d needs the decode engine (use_fused = 2)", cfg.sliding_window);
+    if (kv_fp8() && cfg.use_fused != 2) return fail("FP8 KV pages need the decode engine (use_fused = 2)");
     if (cfg.use_fused == 2) {  // the engine never falls back silently: its arithmetic (Q8_K activations) differs from the Q8_1 paths
       if (!engine_ok()) return fail("decode engine: needs interleaved RoPE, head_dim 128, block 32, q4_k/q5_k/q6_k/q8_0 linears and a decode-layout copy of every linear");
       return forward_engine(b, s);
@@ -1020,7 +1068,7 @@ class Llama {
              (double)cfg.num_experts * cfg.hidden_size * 4.0;
     if (lm_head) t += (double)lm_head->get_qtensor()->nbytes();
     if (wte) { const auto *ti = type_info(wte->get_qtensor()->dtype); t += (double)b * (wte->get_qtensor()->cols / ti->block) * ti->bytes; }
-    t += (double)b * 2.0 * cfg.num_layers * cfg.num_kv_heads * cfg.head_dim * (double)ctx * 2.0;  // bf16 K + V
+    t += (double)b * 2.0 * cfg.num_layers * cfg.num_kv_heads * cfg.head_dim * (double)ctx * (kv_fp8() ? 1.0 : 2.0);  // K + V: 16-bit or FP8 elements
     return t;
   }
 };
@@ -1084,7 +1132,7 @@ extern "C" size_t mrs_llama_workspace_bytes(const mrs_llama_config *cfg) { retur
 extern "C" void *mrs_llama_create(const mrs_llama_config *cfg) {
   if (!cfg || cfg->num_layers <= 0 || cfg->hidden_size <= 0 || cfg->num_heads <= 0 || cfg->num_kv_heads <= 0 ||
       cfg->num_heads % cfg->num_kv_heads || cfg->head_dim <= 0 || cfg->max_batch <= 0 || cfg->max_batch > 8 ||
-      cfg->rot_dim > cfg->head_dim || (cfg->rot_dim & 1) || cfg->num_experts < 0 ||
+      cfg->rot_dim > cfg->head_dim || (cfg->rot_dim & 1) || cfg->num_experts < 0 || cfg->kv_f16 < 0 || cfg->kv_f16 > 2 ||
       (cfg->num_experts > 0 && (cfg->num_experts_per_tok < 1 || cfg->num_experts_per_tok > cfg->num_experts))) {
     mrs_host::fail("mrs_llama_create: invalid config");
     return nullptr;
@@ -1191,6 +1239,7 @@ extern "C" int mrs_llama_set_kv_cache(void *m, int layer, void *k, void *v) {
   l.blocks[layer].key_cache = k; l.blocks[layer].value_cache = v;
   return 0;
 }
+extern "C" int mrs_llama_set_kv_scales(void *m, int layer, float k_scale, float v_scale) { return ((Llama *)m)->set_kv_scales(layer, k_scale, v_scale); }
 extern "C" int mrs_llama_set_buffers(void *m, const mrs_llama_buffers *b) { return ((Llama *)m)->set_buffers(*b); }
 extern "C" int mrs_llama_decode_step(void *m, int b, void *stream) { return ((Llama *)m)->decode_step(b, (hipStream_t)stream); }
 extern "C" int mrs_llama_decode_step_chained(void *m, int b, void *stream) { return ((Llama *)m)->decode_step_chained(b, (hipStream_t)stream); }

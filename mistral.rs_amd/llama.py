@@ -47,7 +47,9 @@ class LlamaConfig:
     # decode engine (csrc/ext_dec.hip: the reference CPU path's arithmetic, Q8_K / Q8_0 activations).  None = whenever the model allows it
     # (use_fused, interleaved RoPE, head_dim 128, block 32, q4_k / q5_k / q6_k / q8_0 linears); False = the round-1 fused kernels (Q8_1)
     decode_engine: bool | None = None
-    kv_dtype: str = "bf16"  # "f16": the reference CPU path's default KV dtype (decode engine only; the MFMA prefill needs bf16 pages)
+    # "f16": the reference CPU path's default KV dtype (decode engine only; the MFMA prefill needs bf16 pages).  "f8e4m3": FP8 E4M3 bytes in the reference's FP8
+    # page layout with one static K and one V scale per layer (Llama.set_kv_scales; 1.0 = uncalibrated): decode engine + exact prompt path only
+    kv_dtype: str = "bf16"
     tp_world_size: int = 1  # tensor parallel: num_heads / num_kv_heads / intermediate_size are the LOCAL (per-rank) sizes
     tp_rank: int = 0
     num_experts: int = 0           # > 0: Mixtral-style sparse MoE FFN in every layer (models/mixtral.rs:236-304)
@@ -117,6 +119,9 @@ class _Cfg(C.Structure):
                                          "num_experts", "num_experts_per_tok", "kv_f16", "sliding_window")]
 
 
+_KV_CODES = {"bf16": 0, "f16": 1, "f8e4m3": 2}  # mrs_llama_config.kv_f16
+
+
 class _PrefillArgs(C.Structure):
     _fields_ = [("token_ids", C.c_void_p), ("positions", C.c_void_p), ("slot_mapping", C.c_void_p), ("block_tables", C.c_void_p),
                 ("context_lens", C.c_void_p), ("logits", C.c_void_p), ("start_pos", C.c_int32), ("workspace", C.c_void_p),
@@ -145,6 +150,7 @@ class Llama:
         L.mrs_llama_destroy.argtypes = [C.c_void_p]
         L.mrs_llama_set_tensor.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64]
         L.mrs_llama_set_kv_cache.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.mrs_llama_set_kv_scales.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float]
         L.mrs_llama_set_buffers.argtypes = [C.c_void_p, C.POINTER(_Bufs)]
         L.mrs_llama_decode_step.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.mrs_llama_forward_logits.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
@@ -177,10 +183,12 @@ class Llama:
         L.mrs_dequantize.argtypes = [C.c_void_p, C.c_int, C.c_longlong, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
         L.mrs_llama_set_bf16_tensor.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
         L.mrs_last_error.restype = C.c_char_p
+        if cfg.kv_dtype not in _KV_CODES:
+            raise ValueError("kv_dtype must be bf16, f16 or f8e4m3")
         c = _Cfg(cfg.hidden_size, cfg.intermediate_size, cfg.num_layers, cfg.num_heads, cfg.num_kv_heads, cfg.head_dim,
                  cfg.vocab_size, cfg.head_dim, int(cfg.rope_interleaved), cfg.rms_eps, cfg.block_size, cfg.max_blocks_per_seq,
                  cfg.max_batch, cfg.max_context_len, int(cfg.use_fused), cfg.tp_world_size, cfg.tp_rank, cfg.num_experts,
-                 cfg.num_experts_per_tok if cfg.num_experts else 0, int(cfg.kv_dtype == "f16"), int(cfg.sliding_window or 0))
+                 cfg.num_experts_per_tok if cfg.num_experts else 0, _KV_CODES[cfg.kv_dtype], int(cfg.sliding_window or 0))
         self._c = c
         self._h = L.mrs_llama_create(C.byref(c))
         if not self._h:
@@ -188,8 +196,6 @@ class Llama:
         self._keep: dict = {}
         if cfg.max_context_len > cfg.max_position_embeddings:
             raise ValueError(f"max_context_len {cfg.max_context_len} exceeds max_position_embeddings {cfg.max_position_embeddings} (the RoPE tables)")
-        if cfg.kv_dtype not in ("bf16", "f16"):
-            raise ValueError("kv_dtype must be bf16 or f16")
         # decode engine: wanted unless switched off; possible while every linear registered so far has a decode layout
         # rotate-half ("neox") RoPE (safetensors Llama / Mistral, RotaryEmbedding::forward with is_gpt_neox): the engine takes it with the q / k rows in pair
         # order (set_tensor permutes them for the decode layout), full rotary only
@@ -197,15 +203,16 @@ class Llama:
             and cfg.num_heads // cfg.num_kv_heads in (1, 2, 4, 8) and (cfg.rope_interleaved or getattr(cfg, "rot_dim", cfg.head_dim) == cfg.head_dim)
         if cfg.decode_engine and not self._engine_wanted:
             raise ValueError("decode_engine needs use_fused, head_dim 128, block_size 32, a GQA group of 1 / 2 / 4 / 8 and (with rotate-half RoPE) full rotary")
-        if cfg.kv_dtype == "f16" and not self._engine_wanted:
-            raise ValueError("f16 KV pages are a decode-engine feature")
+        if cfg.kv_dtype != "bf16" and not self._engine_wanted:
+            raise ValueError(f"{cfg.kv_dtype} KV pages are a decode-engine feature")
         self._engine_ok = self._engine_wanted
         self._mode_set = None
         B, dev = cfg.max_batch, device
         # paged KV cache, bf16, reference layout (cache_engine.rs:458-484); blocks for max_batch full sequences
         self.num_blocks = B * cfg.max_blocks_per_seq
-        x = 8
-        kvt = torch.float16 if cfg.kv_dtype == "f16" else torch.bfloat16
+        # FP8 pages: uint8 codes, 16 dims per K group (the reference's FP8 layout); 16-bit pages: 8
+        x = 16 if cfg.kv_dtype == "f8e4m3" else 8
+        kvt = {"bf16": torch.bfloat16, "f16": torch.float16, "f8e4m3": torch.uint8}[cfg.kv_dtype]
         self.key_caches = [torch.zeros(self.num_blocks, cfg.num_kv_heads, cfg.head_dim // x, cfg.block_size, x, dtype=kvt, device=dev)
                            for _ in range(cfg.num_layers)]
         self.value_caches = [torch.zeros(self.num_blocks, cfg.num_kv_heads, cfg.head_dim, cfg.block_size, dtype=kvt, device=dev)
@@ -248,6 +255,36 @@ class Llama:
                 self._h = None
         except Exception:
             pass
+
+    @property
+    def kv_cache_bytes(self) -> int:
+        """Bytes of all K and V pages of the model."""
+        return sum(t.numel() * t.element_size() for t in self.key_caches + self.value_caches)
+
+    def set_kv_scales(self, k_scale, v_scale) -> None:
+        """FP8 pages: the static scales (code = fp8(x / scale), element = fp8 * scale) -- a scalar for every layer or one value per layer; finite and > 0.  Pages written
+        under other scales keep their codes.  The scales are launch arguments: a captured decode graph is dropped (capture_decode_graph() again).  The prompt path's
+        cache write reads them from device memory, so the device is synchronised first: no launch in flight sees a half-changed pair."""
+        if self.cfg.kv_dtype != "f8e4m3":
+            raise ValueError("set_kv_scales: the model has no FP8 KV pages (kv_dtype='f8e4m3')")
+        n = self.cfg.num_layers
+
+        def per_layer(v, what):
+            a = np.asarray(v, dtype=np.float64).reshape(-1)
+            if a.size == 1:
+                a = np.repeat(a, n)
+            if a.size != n:
+                raise ValueError(f"set_kv_scales: {what} needs 1 or {n} values, got {a.size}")
+            a32 = a.astype(np.float32)
+            if not (np.isfinite(a32).all() and (a32 > 0).all()):
+                raise ValueError(f"set_kv_scales: {what} must be finite and > 0")
+            return a32
+        ks, vs = per_layer(k_scale, "k_scale"), per_layer(v_scale, "v_scale")
+        torch.cuda.synchronize()
+        for i in range(n):
+            self._chk(self._L.mrs_llama_set_kv_scales(self._h, i, float(ks[i]), float(vs[i])))
+        self._graph = None
+        self._replays_left = None
 
     def set_comm(self, comm) -> None:
         """Attach the RCCL communicator (distributed.RcclComm) used for the row-parallel sum all-reduces."""
@@ -406,8 +443,8 @@ class Llama:
     def _set_mode(self) -> None:
         mode = 2 if (self._engine_wanted and self._engine_ok) else int(bool(self.cfg.use_fused))
         if mode != self._mode_set:
-            if self.cfg.kv_dtype == "f16" and mode != 2:
-                raise ValueError("f16 KV pages need the decode engine (a linear has a dtype it does not support)")
+            if self.cfg.kv_dtype != "bf16" and mode != 2:
+                raise ValueError(f"{self.cfg.kv_dtype} KV pages need the decode engine (a linear has a dtype it does not support)")
             self._chk(self._L.mrs_llama_set_mode(self._h, mode))
             self._mode_set = mode
 
@@ -466,7 +503,7 @@ class Llama:
 
     def replay(self) -> None:
         if self._graph is None:
-            raise RuntimeError("replay(): no decode graph is captured (set_p2p() / p2p_sync_error() drop the graph of the old all-reduce route: capture_decode_graph() again)")
+            raise RuntimeError("replay(): no decode graph is captured (set_p2p() / p2p_sync_error() drop the graph of the old all-reduce route, set_kv_scales() the graph of the old scales: capture_decode_graph() again)")
         # the captured step advances device-side state; refuse to run it past the buffers it indexes (tokens_out, block table, RoPE tables)
         if self._replays_left is None:  # one read-back per set_state(): replays that stay inside the context window and the token buffer
             b = getattr(self, "_graph_batch", None) or self.positions.numel()  # only the sequences of the captured batch count (stale entries of earlier, larger batches do not)
@@ -489,7 +526,7 @@ class Llama:
         cfg, dev = self.cfg, self.device
         T = len(tokens)
         if cfg.kv_dtype != "bf16" and not self.prefill_is_exact:
-            raise ValueError("the bf16 MFMA prefill reads and writes bf16 KV pages; use prefill_chunked() with f16 pages")
+            raise ValueError(f"the bf16 MFMA prefill reads and writes bf16 KV pages; use prefill_chunked() with {cfg.kv_dtype} pages")
         if start_pos + T > cfg.max_context_len:
             raise ValueError("prompt does not fit max_context_len")
         pos = torch.arange(start_pos, start_pos + T, dtype=torch.int32, device=dev)

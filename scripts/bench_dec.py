@@ -10,7 +10,103 @@ class Mat(C.Structure):
     _fields_ = [("planes", C.c_void_p), ("type", C.c_int), ("n", C.c_longlong), ("k", C.c_longlong)]
 
 
+def bench_attention(a):
+    """--attn: the engine's attention launches over bf16 and over FP8 (E4M3) pages at Llama-3-8B head counts (32 / 8 heads of 128): decode attention
+    (mrs_dec_attention / mrs_dec_attention_f8) at contexts 512 / 4096 / 32768, batch 1 and 8, and prompt attention (mrs_prefill_attention_exact / _f8) at T = 512 / 2048.
+    us per launch inside one HIP graph over rotating page sets (>= 1 GB of pages or 16 sets: nothing Infinity-Cache resident), and the K / V bytes a launch reads."""
+    import torch
+    import mistralrs_amd  # noqa: F401
+    from mistralrs_amd import _lib
+    dev = torch.device("cuda:0")
+    L = _lib.load("ext")
+    _lib.load("quant"); _lib.load("paged_attn")
+    VP, CI, CF = C.c_void_p, C.c_int, C.c_float
+    L.mrs_decode_attention_max_splits.argtypes = [CI]
+    L.mrs_dec_attention.argtypes = [VP] * 9 + [CI, CF, VP, VP] + [CI] * 11 + [VP]
+    L.mrs_dec_attention_f8.argtypes = [VP] * 9 + [CI, CF, VP, VP] + [CI] * 10 + [CF, CF, VP]
+    L.mrs_prefill_attention_exact.argtypes = [VP] * 6 + [CI] * 8 + [CF, CI, CI, CI, CI, VP]
+    L.mrs_prefill_attention_exact_f8.argtypes = [VP] * 6 + [CI] * 8 + [CF, CI, CI, CI, CF, CF, VP]
+    heads, kvh, hd, bs = 32, 8, 128, 32
+    nq, scale = heads * hd, 1.0 / hd ** 0.5
+
+    def pages(f8, nblocks):
+        if f8:  # codes below 0x40 in magnitude: finite, moderate scores
+            k = torch.randint(0, 0x40, (nblocks, kvh, hd // 16, bs, 16), dtype=torch.uint8, device=dev)
+            v = torch.randint(0, 0x40, (nblocks, kvh, hd, bs), dtype=torch.uint8, device=dev)
+        else:
+            k = (torch.randn(nblocks, kvh, hd // 8, bs, 8, device=dev) * 0.7).to(torch.bfloat16)
+            v = torch.randn(nblocks, kvh, hd, bs, device=dev).to(torch.bfloat16)
+        return k, v
+
+    def timed(fns):
+        for f in fns:
+            assert f(torch.cuda.current_stream().cuda_stream) >= 0
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            for f in fns:
+                f(torch.cuda.current_stream().cuda_stream)
+        g.replay()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(a.reps):
+            g.replay()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1e3 / (a.reps * len(fns))
+
+    for ctx in (512, 4096, 32768):
+        for b in (1, 8):
+            mbs = ctx // bs
+            splits = L.mrs_decode_attention_max_splits(ctx)
+            q = torch.randn(b, nq, device=dev) * 0.5
+            out = torch.empty(b, nq, device=dev)
+            po, pm, pl = torch.zeros(b * heads * splits * hd, device=dev), torch.zeros(b * heads * splits, device=dev), torch.zeros(b * heads * splits, device=dev)
+            ticket = torch.zeros(b * kvh, dtype=torch.int32, device=dev)
+            bt = torch.arange(b * mbs, dtype=torch.int32, device=dev).reshape(b, mbs).contiguous()
+            cl = torch.full((b,), ctx, dtype=torch.int32, device=dev)
+            for f8 in (False, True):
+                kv_bytes = b * ctx * kvh * hd * 2 * (1 if f8 else 2)
+                sets = [pages(f8, b * mbs) for _ in range(max(2, min(16, int(1e9 // kv_bytes))))]
+                if f8:
+                    fns = [lambda st, k=k, v=v: L.mrs_dec_attention_f8(out.data_ptr(), None, ticket.data_ptr(), po.data_ptr(), pm.data_ptr(), pl.data_ptr(), q.data_ptr(), k.data_ptr(),
+                                                                       v.data_ptr(), kvh, scale, bt.data_ptr(), cl.data_ptr(), bs, ctx, b, heads, hd, mbs, nq, kvh * hd * bs, hd * bs, 0, 1.0, 1.0, st)
+                           for k, v in sets]
+                else:
+                    fns = [lambda st, k=k, v=v: L.mrs_dec_attention(out.data_ptr(), None, ticket.data_ptr(), po.data_ptr(), pm.data_ptr(), pl.data_ptr(), q.data_ptr(), k.data_ptr(),
+                                                                    v.data_ptr(), kvh, scale, bt.data_ptr(), cl.data_ptr(), bs, ctx, b, heads, hd, mbs, nq, kvh * hd * bs, hd * bs, 1, 0, st)
+                           for k, v in sets]
+                us = timed(fns)
+                print(json.dumps({"launch": "decode attention", "pages": "f8e4m3" if f8 else "bf16", "ctx": ctx, "b": b, "us": round(us, 2), "kv_MB": round(kv_bytes / 1e6, 2),
+                                  "TBps": round(kv_bytes / us / 1e6, 3), "page_sets": len(sets)}), flush=True)
+                del sets, fns
+    for T in (512, 2048):
+        mbs = T // bs
+        q = torch.randn(T, nq, device=dev) * 0.5
+        out = torch.empty(T, nq, device=dev)
+        bt = torch.arange(mbs, dtype=torch.int32, device=dev)
+        cl = torch.arange(1, T + 1, dtype=torch.int32, device=dev)
+        for f8 in (False, True):
+            sets = [pages(f8, mbs) for _ in range(4)]
+            if f8:
+                fns = [lambda st, k=k, v=v: L.mrs_prefill_attention_exact_f8(q.data_ptr(), k.data_ptr(), v.data_ptr(), bt.data_ptr(), cl.data_ptr(), out.data_ptr(), T, heads, kvh, hd, bs, nq,
+                                                                             kvh * hd * bs, hd * bs, scale, T, 0, T, 1.0, 1.0, st) for k, v in sets]
+            else:
+                fns = [lambda st, k=k, v=v: L.mrs_prefill_attention_exact(q.data_ptr(), k.data_ptr(), v.data_ptr(), bt.data_ptr(), cl.data_ptr(), out.data_ptr(), T, heads, kvh, hd, bs, nq,
+                                                                          kvh * hd * bs, hd * bs, scale, T, 1, 0, T, st) for k, v in sets]
+            us = timed(fns)
+            print(json.dumps({"launch": "prompt attention", "pages": "f8e4m3" if f8 else "bf16", "T": T, "us": round(us, 2),
+                              "kv_MB_once": round(T * kvh * hd * 2 * (1 if f8 else 2) / 1e6, 2)}), flush=True)
+            del sets, fns
+
+
 def main():
+    if "--attn" in sys.argv:
+        ap = argparse.ArgumentParser()
+        ap.add_argument("--attn", action="store_true", help="attention launches over bf16 and FP8 pages instead of the GEMV phases (bench_attention)")
+        ap.add_argument("--reps", type=int, default=20)
+        return bench_attention(ap.parse_args())
     ap = argparse.ArgumentParser()
     ap.add_argument("--b", type=int, default=1)
     ap.add_argument("--reps", type=int, default=4)
