@@ -34,9 +34,11 @@ struct GemvArgs {
                               // logits in a launch of its own, sample_cuda_top1_row's role, mistralrs-core/src/ops.rs:2206); nullptr = off
   unsigned long long *tl;
 };
-// order-preserving key of (value, index): larger value wins, then the smaller index (== ext_decode.hip pack_max)
+// order-preserving key of (value, index): larger value wins, then the smaller index; -0.0 and +0.0 are one value, as under argmax_f32's `>` (sampler.rs:513-529)
+// (== ext_decode.hip pack_max)
 __device__ __forceinline__ unsigned long long pack_max_key(float v, int idx) {
   unsigned u = __float_as_uint(v);
+  u = u == 0x80000000u ? 0u : u;
   u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
   return ((unsigned long long)u << 32) | (unsigned)(0x7fffffff - idx);
 }

@@ -402,10 +402,13 @@ struct SampleArgs {
   unsigned long long *scratch;  // [b] packed (value, index) maxima, zeroed by the launcher
 };
 
+// order-preserving key of (value, index): larger value wins, then the smaller index; -0.0 and +0.0 are one value, as under argmax_f32's `>` (sampler.rs:513-529)
+// (== dec_gemv.cuh pack_max_key)
 __device__ __forceinline__ unsigned long long pack_max(float v, int idx) {
   unsigned u = __float_as_uint(v);
-  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // order-preserving map
-  return ((unsigned long long)u << 32) | (unsigned)(0x7fffffff - idx);  // ties -> smaller index
+  u = u == 0x80000000u ? 0u : u;
+  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  return ((unsigned long long)u << 32) | (unsigned)(0x7fffffff - idx);
 }
 
 // round 5: 16-byte loads, one contiguous slice per workgroup (the round-4 kernel walked the row with 4-byte strided loads from 128 workgroups: 8 us for 513 KB);

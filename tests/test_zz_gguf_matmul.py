@@ -52,7 +52,8 @@ def test_forward_dispatch_and_bias(oracle, dev, tag):
 
 
 def test_embedding_gather_matches_dequantize_gather(oracle, dev):
-    """gguf/mod.rs:815-846: quantize -> embedding gather == quantize -> dequantize -> gather, <= 1e-6; values ((i % 37) - 18) / 7."""
+    """gguf/mod.rs:815-846: quantize -> embedding gather == quantize -> dequantize -> gather, <= 1e-6 in the reference's test; values ((i % 37) - 18) / 7.  Here the
+    two are the same f32 expressions on the same block fields, so the bar is equality (tests/test_greedy_step.py holds mrs_embedding to it for every table type)."""
     import torch
     from mistralrs_amd.gguf import GgmlDType, QTensor
     from mistralrs_amd.gguf.matmul import GgufMatMul
@@ -64,7 +65,7 @@ def test_embedding_gather_matches_dequantize_gather(oracle, dev):
         ids = torch.tensor([[3, 0, 7], [7, 1, 3]], device=dev)
         got = m.embedding_forward_raw(ids)
         want = m.dequantize_w()[ids.reshape(-1).long()].reshape(2, 3, dim)
-        assert got.shape == (2, 3, dim) and float((got - want).abs().max()) <= 1e-6
+        assert got.shape == (2, 3, dim) and torch.equal(got, want)
 
 
 def test_apply_isq_and_fallback(oracle, dev):
