@@ -7,6 +7,7 @@
  */
 #ifndef MISTRALRS_CORE_H
 #define MISTRALRS_CORE_H
+#include <stddef.h>
 #include <stdint.h>
 #ifdef __cplusplus
 extern "C" {
@@ -86,6 +87,28 @@ void categorical_large_f32_packed_batched(const float *input, const float *inv_t
 void mrs_nucleus_large_f32_packed_batched(const float *input, const float *inv_temperatures, const float *uniforms, const float *top_ps, const float *min_ps,
                                           float *block_values, float *block_sums, float *packed_out, int nrows, int ncols, int chunk_size, int nblocks,
                                           int64_t stream);
+
+/* Speculative decoding, the verifier: the rounds of nseq sequences in one launch group (this library's own symbol: the reference loops on the host over full-vocabulary
+ * probability vectors -- mistralrs-core/src/speculative/verifier.rs:44-115 greedy verification, :200-290 the accept loop, :339-473 the stochastic rule).  Sequence s
+ * owns the rows seq_rows[s] .. seq_rows[s + 1] (1..8 of them) of target_logits [total_rows][ncols] f32; with n = rows - 1 drafts, row i judges draft_ids[row i] and the
+ * last row is the bonus row (its draft_ids entry is ignored); n = 0 is a plain draw.  modes[s]: 0 greedy, 1 temperature; inv_temperatures[s]; uniforms [total_rows][2] =
+ * (the accept draw u0, the draw u1 used if this row ends the round); draft_logits [total_rows][ncols] or NULL (a deterministic proposer: q is one-hot on the draft).
+ * Outputs: n_accepted [nseq], out_tokens [nseq][8] = the accepted drafts, then the continuation token, then -1.
+ *   greedy: a row's winner is what mrs_sample_greedy_advance picks on it (largest value, lowest index on ties, -0.0 ranks with +0.0); n_accepted = the longest prefix with
+ *   winner == draft, the continuation is the winner of row n_accepted.
+ *   temperature: p = softmax(target * inv_t), q = softmax(draft * inv_t), each as the categorical entry computes it (gmax, denom in chunk order), p_d = expf(x_d * inv_t -
+ *   gmax) / denom; accept = q_d > 0 ? min(1, p_d / q_d) : (p_d > 0 ? 1 : 0) (draft_logits NULL: q_d = 1), accepted iff u0 < accept.  At the first rejected row the
+ *   continuation inverts the cumulative sums of max(p - q, 0) (NULL: p with the draft zeroed) at u1 -- chunk masses in chunk order, the categorical entry's rule inside
+ *   the chunk -- or is drawn from p when that sum is not positive.  With every draft accepted the bonus row is categorical_large_f32_packed_batched's draw at u1, bit for bit.
+ * Rows after the one that ends the round are never read and may hold NaN.  A sequence reports n_accepted = -1 (and eight -1 tokens) when a row that decides is unusable --
+ * a NaN in it (either mode); in temperature mode also a +inf logit, a row of -inf, inv_t not finite or <= 0, u0 / u1 outside [0, 1), a draft id outside the row -- or when
+ * its row count is outside 1..8 or its mode unknown; other sequences are unaffected.  The caller owns `workspace`, >= mrs_spec_verify_workspace_bytes(total_rows, nseq,
+ * nblocks) bytes, 8-byte aligned.  Returns without launching (nothing is written) when nseq < 1, total_rows < nseq or > 8 * nseq or > 65535, the workspace is too small,
+ * or on the shapes the categorical entry refuses.  Four launches on the caller's stream, no allocation. */
+size_t mrs_spec_verify_workspace_bytes(int total_rows, int nseq, int nblocks);
+void mrs_spec_verify_f32_batched(const float *target_logits, const float *draft_logits, const int32_t *draft_ids, const int32_t *seq_rows, const int32_t *modes,
+                                 const float *inv_temperatures, const float *uniforms, void *workspace, size_t workspace_bytes, int32_t *n_accepted, int32_t *out_tokens,
+                                 int nseq, int total_rows, int ncols, int chunk_size, int nblocks, int64_t stream);
 
 /* Sampler pre-processing: dst [n] = x [n] (f32), then for the n_tokens listed token ids (ids >= n ignored): penalties -- skipped where count <= 0;
  * v -= count * frequency_penalty + presence_penalty; if repetition_penalty != 1: v = v > 0 ? v / rp : v * rp -- or additive biases.

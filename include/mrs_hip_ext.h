@@ -157,6 +157,18 @@ int mrs_sample_greedy_advance(const float *logits, int vocab, int b, int32_t *ne
                               int tokens_out_stride, int32_t *step_counter, int32_t *positions, uint32_t *context_lens,
                               int64_t *slot_mapping, const uint32_t *block_tables, int max_blocks, int block_size,
                               void *scratch, void *stream);
+/* Speculative decoding, after mrs_spec_verify_f32_batched (include/mistralrs_core.h) judged a round of sequence `seq`: from n_accepted [1] and out_tokens [8] of that
+ * sequence the n_accepted + 1 emitted tokens go to tokens_out[seq] at step_counter (tokens past tokens_out_stride are dropped), step_counter grows by that count, and
+ * input_ids / positions / context_lens / slot_mapping of `seq` point at the continuation token at position p + n_accepted + 1 (a position past the block table gets
+ * slot -1).  K/V written for rejected drafts stays in the pages beyond the new context length: never read, overwritten by the next round.  n_accepted outside 0..7
+ * changes nothing.  Role of the accept loop's bookkeeping, mistralrs-core/src/speculative/verifier.rs:200-290. */
+int mrs_spec_advance(const int32_t *n_accepted, const int32_t *out_tokens, int seq, int32_t *input_ids, int32_t *tokens_out, int tokens_out_stride,
+                     int32_t *step_counter, int32_t *positions, uint32_t *context_lens, int64_t *slot_mapping, const uint32_t *block_tables, int max_blocks,
+                     int block_size, void *stream);
+/* The inputs of a verify step: n_rows <= 8 rows of sequence `seq` as a batch of their own -- ids[0] = input_ids[seq], pos[r] = positions[seq] + r, ctx[r] = pos[r] + 1,
+ * slots[r] from the sequence's block-table row (-1 past it), tables [n_rows][max_blocks] = copies of that row.  Reads the decode state, writes only the five outputs. */
+int mrs_spec_verify_prep(const int32_t *input_ids, const int32_t *positions, const uint32_t *block_tables, int seq, int n_rows, int max_blocks, int block_size,
+                         int32_t *ids, int32_t *pos, uint32_t *ctx, int64_t *slots, uint32_t *tables, void *stream);
 
 /* ---------------------------------------------------------------- mixture of experts, decode (Mixtral: SparseMoeBlock::forward,
  * mistralrs-core/src/models/mixtral.rs:280-304; router = moe_router_topk, ops.rs:259-336; expert GEMVs = the indexed kernels of
@@ -342,6 +354,14 @@ int mrs_llama_embed_state(void *model, int b, void *stream);
 int mrs_llama_chained_ok(void *model, int b);
 /* same graph without sampling: leaves logits [b, vocab] (parity tests read them) */
 int mrs_llama_forward_logits(void *model, int b, void *stream);
+/* Speculative decoding, the verify step (decode engine only): n_rows <= min(8, max_batch) rows of sequence `seq` -- its anchor token (input_ids[seq] at positions[seq])
+ * and the n_rows - 1 drafts the caller wrote to mrs_llama_verify_ids(model)[1 ..] (device int32 [9]: ids + 1 is a whole draft_ids [8] for the verifier, whose last
+ * entry nobody reads) at the following positions -- through the batched decode launches;
+ * every row attends to [0, its position].  Leaves logits[:n_rows] (row i = the distribution after draft i - 1) and K/V of all rows in the sequence's pages.  The decode
+ * state and every other sequence's block-table row are only read: the step runs on a verify-only table in the workspace (mrs_spec_verify_prep).  The step itself neither
+ * allocates nor synchronises; capturing it in a graph is untested.  Role of the target pass of mistralrs-core/src/speculative/verifier.rs:44-115. */
+int mrs_llama_verify_step(void *model, int seq, int n_rows, void *stream);
+int32_t *mrs_llama_verify_ids(void *model);
 /* Prefill of T prompt tokens of ONE sequence (role of the prompt branch of Llama::forward_embeds + PagedAttention::forward,
  * models/llama.rs:487-518, paged_attention/layers/paged_attention.rs:1413-1475): per layer RMSNorm -> q/k/v GEMMs (bf16 MFMA,
  * mrs_gemm_q_f32) -> RoPE -> reshape_and_cache -> causal attention over the freshly written pages -> o_proj GEMM (+residual) ->

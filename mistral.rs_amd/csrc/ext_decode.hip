@@ -464,6 +464,55 @@ __global__ void __launch_bounds__(64) sample_advance_kernel(const SampleArgs a) 
   if (c == 0) *a.step_counter = step + 1;
 }
 
+// speculative decoding: the state advance after a verified round of ONE sequence (the role of the accept loop's bookkeeping, mistralrs-core/src/speculative/mod.rs: the
+// accepted tokens are appended and the caches rolled back to the accepted length).  From n_accepted and out_tokens [8] of mrs_spec_verify_f32_batched: the n_accepted + 1
+// emitted tokens go to tokens_out at step_counter, step_counter grows by that count, and the decode state points at the continuation token at position p + n_accepted + 1.
+// K/V that the verify step wrote for rejected drafts stays in the pages BEYOND the new context length: it is never read (attention stops at context_lens) and the next
+// round overwrites it.  Same guards as sample_advance_kernel: tokens past tokens_out_stride are dropped, a position past the block table gets slot -1.
+// n_accepted outside 0..7 (the verifier's -1 for an unusable round): nothing changes.
+struct SpecAdvanceArgs {
+  const int32_t *n_accepted, *out_tokens;
+  int seq;
+  int32_t *input_ids, *tokens_out; int tokens_out_stride; int32_t *step_counter;
+  int32_t *positions; uint32_t *context_lens; int64_t *slot_mapping; const uint32_t *block_tables; int max_blocks; int block_size;
+};
+__global__ void __launch_bounds__(64) spec_advance_kernel(const SpecAdvanceArgs a) {
+  const int t = threadIdx.x, c = a.seq;
+  const int n = a.n_accepted[0];
+  if (n < 0 || n > 7) return;
+  const int step = *a.step_counter;
+  if (t <= n && a.tokens_out && step + t < a.tokens_out_stride) a.tokens_out[(size_t)c * a.tokens_out_stride + step + t] = a.out_tokens[t];
+  __syncthreads();
+  if (t != 0) return;
+  *a.step_counter = step + n + 1;
+  a.input_ids[c] = a.out_tokens[n];
+  const int pos = a.positions[c] + n + 1;
+  a.positions[c] = pos;
+  a.context_lens[c] = (uint32_t)pos + 1;
+  const int blk = pos / a.block_size;
+  a.slot_mapping[c] = blk < a.max_blocks ? (int64_t)a.block_tables[(size_t)c * a.max_blocks + blk] * a.block_size + pos % a.block_size : (int64_t)-1;
+}
+
+// speculative decoding: the inputs of a verify step (mrs_llama_verify_step) -- n_rows rows of ONE sequence as a batch of their own, without touching the decode state or
+// any other sequence's block-table row.  Row r is the sequence's token at position p + r: ids[0] = input_ids[seq] (the anchor; the caller wrote the drafts to ids[1..]),
+// positions[r] = p + r, context_lens[r] = p + r + 1, slot r from the sequence's block-table row (-1 past it), and tables[r] = a copy of that row.
+struct SpecPrepArgs {
+  const int32_t *input_ids, *positions; const uint32_t *block_tables; int seq, n_rows, max_blocks, block_size;
+  int32_t *ids, *pos; uint32_t *ctx; int64_t *slots; uint32_t *tables;
+};
+__global__ void __launch_bounds__(256) spec_prep_kernel(const SpecPrepArgs a) {
+  const int r = blockIdx.x;
+  const uint32_t *src = a.block_tables + (size_t)a.seq * a.max_blocks;
+  for (int i = threadIdx.x; i < a.max_blocks; i += 256) a.tables[(size_t)r * a.max_blocks + i] = src[i];
+  if (threadIdx.x != 0) return;
+  const int pos = a.positions[a.seq] + r;
+  if (r == 0) a.ids[0] = a.input_ids[a.seq];
+  a.pos[r] = pos;
+  a.ctx[r] = (uint32_t)pos + 1;
+  const int blk = pos / a.block_size;
+  a.slots[r] = blk < a.max_blocks ? (int64_t)src[blk] * a.block_size + pos % a.block_size : (int64_t)-1;
+}
+
 // round 6, batch 1: sample_advance_kernel + the NEXT step's embedding gather in one launch (the captured decode graph then opens with layer 0's qkv: the step is two
 // launches shorter -- argmax_partial_kernel lives in lm_head's epilogue, mrs_dec_proj_argmax, and embedding_kernel here).  a.scratch[0] holds the packed maximum.
 struct EmbedNext { const uint8_t *table; int type; float *h; int K; };
@@ -818,6 +867,24 @@ extern "C" int mrs_sample_advance_embed(int32_t *next_ids, int32_t *tokens_out, 
                (unsigned long long *)scratch};
   EmbedNext e{(const uint8_t *)table, type, h_next, K};
   hipLaunchKernelGGL(sample_advance_embed_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a, e);
+  return 0;
+}
+
+extern "C" int mrs_spec_advance(const int32_t *n_accepted, const int32_t *out_tokens, int seq, int32_t *input_ids, int32_t *tokens_out, int tokens_out_stride,
+                                int32_t *step_counter, int32_t *positions, uint32_t *context_lens, int64_t *slot_mapping, const uint32_t *block_tables, int max_blocks,
+                                int block_size, void *stream) {
+  if (!n_accepted || !out_tokens || seq < 0 || max_blocks <= 0 || block_size <= 0) return -1;
+  SpecAdvanceArgs a{n_accepted, out_tokens, seq, input_ids, tokens_out, tokens_out_stride, step_counter, positions, context_lens, slot_mapping, block_tables, max_blocks,
+                    block_size};
+  hipLaunchKernelGGL(spec_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, a);
+  return 0;
+}
+
+extern "C" int mrs_spec_verify_prep(const int32_t *input_ids, const int32_t *positions, const uint32_t *block_tables, int seq, int n_rows, int max_blocks, int block_size,
+                                    int32_t *ids, int32_t *pos, uint32_t *ctx, int64_t *slots, uint32_t *tables, void *stream) {
+  if (seq < 0 || n_rows < 1 || n_rows > 8 || max_blocks <= 0 || block_size <= 0) return -1;
+  SpecPrepArgs a{input_ids, positions, block_tables, seq, n_rows, max_blocks, block_size, ids, pos, ctx, slots, tables};
+  hipLaunchKernelGGL(spec_prep_kernel, dim3(n_rows), dim3(256), 0, (hipStream_t)stream, a);
   return 0;
 }
 

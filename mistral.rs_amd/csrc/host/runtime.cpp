@@ -210,6 +210,11 @@ struct Workspace {  // carve-up of the caller's scratch
   unsigned *attn_ticket;    // decode engine: [max_batch][kv heads] arrival counters of mrs_dec_attention (zero at rest)
   float *kv_scales;         // FP8 pages: [layers][2] the static k / v scales as device floats (reshape_and_cache reads them on the device)
   void *act_img;            // decode engine, batched steps: the activation image of a phase, built once (mrs_dec_act_image -> mrs_dec_*_img); hidden or ffn width, <= 8 columns
+  // speculative decoding: the inputs of a verify step (mrs_spec_verify_prep) -- 8 rows of ONE sequence as a batch of their own, next to the decode state
+  int32_t *verify_ids, *verify_pos;  // ids [9]: the anchor token + the caller's drafts, and one entry more so that ids + 1 is a whole draft_ids [8] for the verifier; positions [8]
+  uint32_t *verify_ctx;              // [8]
+  int64_t *verify_slots;             // [8]
+  uint32_t *verify_tables;           // [8][max_blocks_per_seq]: copies of the sequence's block-table row
 };
 
 class Llama {
@@ -264,6 +269,9 @@ class Llama {
       w.moe_router_scratch = a.take(mrs_moe_router_split_scratch_bytes((int)B, (int)c.num_experts));
     }
     w.kv_scales = a.take<float>((size_t)c.num_layers * 2 * 4);
+    w.verify_slots = a.take<int64_t>(8 * 8);
+    w.verify_ids = a.take<int32_t>(9 * 4); w.verify_pos = a.take<int32_t>(8 * 4); w.verify_ctx = a.take<uint32_t>(8 * 4);
+    w.verify_tables = a.take<uint32_t>(8 * (size_t)c.max_blocks_per_seq * 4);
     return a.off;
   }
   static size_t workspace_bytes(const mrs_llama_config &c) { Workspace w{}; return lay_out(c, nullptr, w) + WORKSPACE_SLACK; }
@@ -486,7 +494,7 @@ class Llama {
   }
   // RmsNorm(h) -> q (f32, RoPE applied) + k / v into the layer's pages.  The matrix cores only when all three tensors qualify and RoPE is interleaved (a rotate-half pair
   // spans two panels); rotate-half: the caller registered q / k decode planes in pair order (mrs_dec_qkv_neox; llama.py permutes the rows before the repack)
-  int qkv_phase(const Block &bl, int b, hipStream_t s) const {
+  int qkv_phase(const mrs_llama_buffers &in, const Block &bl, int b, hipStream_t s) const {  // `in`: the step's inputs (the decode state, or a verify step's rows)
     const int d = cfg.hidden_size, hd = cfg.head_dim, rp = cfg.rot_dim / 2, kvh = cfg.num_kv_heads, bs = cfg.block_size, kvd = engine_kv_dtype();
     const Lin q = lin(bl.dq, bl.q_proj, d), k = lin(bl.dk, bl.k_proj, d), v = lin(bl.dv, bl.v_proj, d);
     Route r = std::min(route(q, b), std::min(route(k, b), route(v, b)));
@@ -496,21 +504,21 @@ class Llama {
       const float ks = bl.k_scale, vs = bl.v_scale;
       switch (r) {
       case R_INLINE: return (cfg.rope_interleaved ? mrs_dec_qkv_f8 : mrs_dec_qkv_neox_f8)(q.mat, k.mat, v.mat, ws.h, d, bl.input_layernorm, cfg.rms_eps, ws.q, bl.key_cache,
-                                                                                        bl.value_cache, bufs.slot_mapping, bufs.positions, bufs.cos_table, bufs.sin_table, hd, rp,
+                                                                                        bl.value_cache, in.slot_mapping, in.positions, in.cos_table, in.sin_table, hd, rp,
                                                                                         kvh, bs, b, ks, vs, s);
-      case R_IMG_VALU: return mrs_dec_qkv_img_f8(q.mat, k.mat, v.mat, ws.act_img, ws.q, bl.key_cache, bl.value_cache, bufs.slot_mapping, bufs.positions, bufs.cos_table,
-                                               bufs.sin_table, hd, rp, kvh, bs, b, cfg.rope_interleaved ? 0 : 1, ks, vs, s);
+      case R_IMG_VALU: return mrs_dec_qkv_img_f8(q.mat, k.mat, v.mat, ws.act_img, ws.q, bl.key_cache, bl.value_cache, in.slot_mapping, in.positions, in.cos_table,
+                                               in.sin_table, hd, rp, kvh, bs, b, cfg.rope_interleaved ? 0 : 1, ks, vs, s);
       default: return mrs_dec_mm_qkv_f8(q.qi, q.mat->type, (int)q.mat->n, k.qi, k.mat->type, (int)k.mat->n, v.qi, v.mat->type, (int)v.mat->n, d, ws.act_img, ws.q, bl.key_cache,
-                                        bl.value_cache, bufs.slot_mapping, bufs.positions, bufs.cos_table, bufs.sin_table, hd, rp, kvh, bs, b, ks, vs, s);
+                                        bl.value_cache, in.slot_mapping, in.positions, in.cos_table, in.sin_table, hd, rp, kvh, bs, b, ks, vs, s);
       }
     }
     switch (r) {
     case R_INLINE: return (cfg.rope_interleaved ? mrs_dec_qkv : mrs_dec_qkv_neox)(q.mat, k.mat, v.mat, ws.h, d, bl.input_layernorm, cfg.rms_eps, ws.q, bl.key_cache, bl.value_cache,
-                                                                              bufs.slot_mapping, bufs.positions, bufs.cos_table, bufs.sin_table, hd, rp, kvh, bs, kvd, b, s);
-    case R_IMG_VALU: return mrs_dec_qkv_img(q.mat, k.mat, v.mat, ws.act_img, ws.q, bl.key_cache, bl.value_cache, bufs.slot_mapping, bufs.positions, bufs.cos_table, bufs.sin_table,
+                                                                              in.slot_mapping, in.positions, in.cos_table, in.sin_table, hd, rp, kvh, bs, kvd, b, s);
+    case R_IMG_VALU: return mrs_dec_qkv_img(q.mat, k.mat, v.mat, ws.act_img, ws.q, bl.key_cache, bl.value_cache, in.slot_mapping, in.positions, in.cos_table, in.sin_table,
                                           hd, rp, kvh, bs, kvd, b, cfg.rope_interleaved ? 0 : 1, s);
     default: return mrs_dec_mm_qkv(q.qi, q.mat->type, (int)q.mat->n, k.qi, k.mat->type, (int)k.mat->n, v.qi, v.mat->type, (int)v.mat->n, d, ws.act_img, ws.q, bl.key_cache,
-                                   bl.value_cache, bufs.slot_mapping, bufs.positions, bufs.cos_table, bufs.sin_table, hd, rp, kvh, bs, kvd, b, s);
+                                   bl.value_cache, in.slot_mapping, in.positions, in.cos_table, in.sin_table, hd, rp, kvh, bs, kvd, b, s);
     }
   }
   // out [b][n] = W . x (mode 0) or out * rs + W . x (mode 1): o_proj, down, lm_head.  The source is x [b][k] f32 (-> RmsNorm when norm_w), or -- x == nullptr -- an image
@@ -542,23 +550,25 @@ class Llama {
 
   // chained (round 6, batch 1): ws.h already holds the embedding row of input_ids (the previous step's mrs_sample_advance_embed, or mrs_llama_embed_state after the host
   // changed the state) and lm_head folds the arg-max into its epilogue: the captured step is two launches shorter (no embedding_kernel, no argmax_partial_kernel)
-  int forward_engine(int b, hipStream_t s, bool chained = false) const {
+  // `in`: the inputs of the step -- the decode state (bufs), or the rows of a verify step (verify_step below).  Named apart from the member on purpose.
+  int forward_engine(int b, hipStream_t s, bool chained = false) const { return forward_engine(bufs, b, s, chained); }
+  int forward_engine(const mrs_llama_buffers &in, int b, hipStream_t s, bool chained) const {
     const float rs = 1.0f / (float)std::max(1, (int)cfg.world_size);
     const int d = cfg.hidden_size, hd = cfg.head_dim, nq = cfg.num_heads * hd, ff = cfg.intermediate_size;
     const int bs = cfg.block_size, kvh = cfg.num_kv_heads;
     const AttnGeom ag = attn_geom();
     if (chained && b != 1) return fail("chained decode step: batch 1 only");
-    if (!chained && wte->embedding_forward_raw(bufs.input_ids, b, ws.h, s)) return -1;
+    if (!chained && wte->embedding_forward_raw(in.input_ids, b, ws.h, s)) return -1;
     for (const Block &bl : blocks) {
-      if (qkv_phase(bl, b, s)) return fail("q / k / v phase refused the layer");
+      if (qkv_phase(in, bl, b, s)) return fail("q / k / v phase refused the layer");
       // one launch: splits + last-arriver merge; even GQA groups hand o_proj the Q8_K image of the result (Q8_0 weights take Q8_0 activations: f32 result)
       const bool want_img = bl.dout.type != 8 && (cfg.num_heads / kvh) % 2 == 0 && mrs_dec_act_image_bytes(nq, b) <= mrs_dec_proj_img_max_bytes();
       const int rc2 = kv_fp8()
           ? mrs_dec_attention_f8(want_img ? nullptr : ws.attn, want_img ? ws.attn_img : nullptr, ws.attn_ticket, (float *)ws.attn_ws, ws.max_logits, ws.exp_sums, ws.q,
-                                 bl.key_cache, bl.value_cache, kvh, ag.scale, bufs.block_tables, bufs.context_lens, bs, ag.eff_max, b, cfg.num_heads, hd,
+                                 bl.key_cache, bl.value_cache, kvh, ag.scale, in.block_tables, in.context_lens, bs, ag.eff_max, b, cfg.num_heads, hd,
                                  cfg.max_blocks_per_seq, nq, ag.block_stride, ag.head_stride, cfg.sliding_window, bl.k_scale, bl.v_scale, s)
           : mrs_dec_attention(want_img ? nullptr : ws.attn, want_img ? ws.attn_img : nullptr, ws.attn_ticket, (float *)ws.attn_ws, ws.max_logits, ws.exp_sums, ws.q,
-                              bl.key_cache, bl.value_cache, kvh, ag.scale, bufs.block_tables, bufs.context_lens, bs, ag.eff_max, b, cfg.num_heads, hd,
+                              bl.key_cache, bl.value_cache, kvh, ag.scale, in.block_tables, in.context_lens, bs, ag.eff_max, b, cfg.num_heads, hd,
                               cfg.max_blocks_per_seq, nq, ag.block_stride, ag.head_stride, ag.kvd, cfg.sliding_window, s);
       if (rc2 < 0) return fail("mrs_dec_attention refused the shape");
       // TP: h <- h / world + W_o . attn on every rank, then ONE sum all-reduce of h (the residual add stays fused, as in forward_fused).  An f32 attention result (odd GQA
@@ -602,8 +612,8 @@ class Llama {
         return fail("down_proj failed: %s", g_last_error.c_str());
     }
     const Lin lm = lin(dlm_head, lm_head, d);
-    const int lrc = chained ? mrs_dec_proj_argmax(lm.mat, cfg.vocab_size, ws.h, d, ln_f, cfg.rms_eps, bufs.logits, cfg.vocab_size, ws.sample_scratch, s)
-                            : proj_phase(lm, cfg.vocab_size, ws.h, ln_f, nullptr, bufs.logits, 0, 1.0f, b, s, route(lm, b));
+    const int lrc = chained ? mrs_dec_proj_argmax(lm.mat, cfg.vocab_size, ws.h, d, ln_f, cfg.rms_eps, in.logits, cfg.vocab_size, ws.sample_scratch, s)
+                            : proj_phase(lm, cfg.vocab_size, ws.h, ln_f, nullptr, in.logits, 0, 1.0f, b, s, route(lm, b));
     if (lrc) return fail("lm_head refused");
     return 0;
   }
@@ -1036,6 +1046,23 @@ class Llama {
     return 0;
   }
 
+  // ---- speculative decoding, the verify step: n_rows rows of sequence `seq` (its anchor token + the drafts in ws.verify_ids[1..]) at consecutive positions through the
+  //      batched engine launches.  One small launch gathers the rows' inputs next to the decode state (ws.verify_*, a verify-only block table); forward_engine then reads
+  //      THEM instead of bufs: no other sequence's block-table row is touched and nothing is saved or restored.  Nothing here allocates or synchronises, but capturing
+  //      the step in a graph is untested.  Leaves logits[:n_rows].
+  int verify_step(int seq, int n_rows, hipStream_t s) const {
+    if (check_ready(1)) return -1;
+    if (cfg.use_fused != 2 || !engine_ok()) return fail("verify step: needs the decode engine (use_fused = 2 and a decode-layout copy of every linear)");
+    if (seq < 0 || seq >= cfg.max_batch) return fail("verify step: sequence %d outside the batch of %d", seq, cfg.max_batch);
+    if (n_rows < 1 || n_rows > std::min(8, (int)cfg.max_batch)) return fail("verify step: %d rows, at most min(8, max_batch = %d)", n_rows, cfg.max_batch);
+    if (mrs_spec_verify_prep(bufs.input_ids, bufs.positions, bufs.block_tables, seq, n_rows, cfg.max_blocks_per_seq, cfg.block_size, ws.verify_ids, ws.verify_pos,
+                             ws.verify_ctx, ws.verify_slots, ws.verify_tables, s))
+      return fail("mrs_spec_verify_prep refused");
+    mrs_llama_buffers vb = bufs;
+    vb.input_ids = ws.verify_ids; vb.positions = ws.verify_pos; vb.context_lens = ws.verify_ctx; vb.slot_mapping = ws.verify_slots; vb.block_tables = ws.verify_tables;
+    return forward_engine(vb, n_rows, s, false);
+  }
+
   // ---- the chained greedy step (round 6): forward_engine without the embedding launch + lm_head with the arg-max in its epilogue + ONE launch that samples, advances
   //      the device-resident state and gathers the NEXT token's embedding row into ws.h.  Same logits, same token as decode_step (tests/test_dec_model.py).
   bool chained_ok(int b) const {
@@ -1246,6 +1273,8 @@ extern "C" int mrs_llama_decode_step_chained(void *m, int b, void *stream) { ret
 extern "C" int mrs_llama_embed_state(void *m, int b, void *stream) { return ((Llama *)m)->embed_state(b, (hipStream_t)stream); }
 extern "C" int mrs_llama_chained_ok(void *m, int b) { return ((Llama *)m)->chained_ok(b) ? 1 : 0; }
 extern "C" int mrs_llama_forward_logits(void *m, int b, void *stream) { return ((Llama *)m)->forward_logits(b, (hipStream_t)stream); }
+extern "C" int mrs_llama_verify_step(void *m, int seq, int n_rows, void *stream) { return ((Llama *)m)->verify_step(seq, n_rows, (hipStream_t)stream); }
+extern "C" int32_t *mrs_llama_verify_ids(void *m) { return ((Llama *)m)->have_bufs ? ((Llama *)m)->ws.verify_ids : nullptr; }
 extern "C" double mrs_llama_decode_bytes(void *m, int b, int ctx) { return ((Llama *)m)->decode_bytes(b, ctx); }
 extern "C" size_t mrs_llama_prefill_workspace_bytes(const mrs_llama_config *cfg, int T) { return Llama::prefill_workspace_bytes(*cfg, T); }
 extern "C" int mrs_llama_prefill(void *m, const mrs_llama_prefill_args *a, int T, void *stream) {

@@ -127,7 +127,9 @@ __device__ __forceinline__ float chunk_softmax_share(const float (&v)[MAXV], int
   return block_sum_ref_order(local_sum, s_warp_sums);
 }
 // workgroup max of the threads' `m` with a carried NaN flag (fmaxf drops a NaN, so a thread that met one passes nan = true and keeps it out of m): every thread gets
-// the max of the rest and, in `any_nan`, the OR of the flags.  A max and an OR: the fold order is free.  One barrier; one call per kernel (the LDS slots are not recycled).
+// the max of the rest and, in `any_nan`, the OR of the flags.  A max and an OR: the fold order is free.  One barrier.  The LDS slots are not recycled inside
+// the call: a kernel that calls it again (spec_stage1_kernel, row_preamble in a loop) must put a barrier between one call's reads of the slots -- they end where the call
+// returns -- and the next call's writes (chunk_softmax_share's two barriers, or a __syncthreads after the preamble, do that).
 template <int WAVES> __device__ __forceinline__ float block_max_nan(float m, bool nan, bool &any_nan) {
   __shared__ float s_wmax[WAVES];
   __shared__ int s_wnan[WAVES];
@@ -522,21 +524,16 @@ __device__ __forceinline__ void store_nan_row(float *packed, int n) {
   for (int i = 0; i < n; ++i) packed[i] = NAN;
 }
 
-__global__ void __launch_bounds__(NT) cat_stage2_kernel(CatArgs a) {
-  __shared__ float s_cum[CAT_MAXB];  // chunk masses, then their running sums
+// ---- the inversion of running chunk sums at a uniform, shared by cat_stage2_kernel and the speculative verifier below (all threads call; the token is valid in
+// thread 0, -1 = no token).  `s_cum` holds the running sums of the first min(nb, CAT_MAXB) chunk masses, `denom` their total over all nb chunks (thread 0), mass(b) gives
+// the mass of a chunk beyond the staged ones, weight(i) the weight of token i.  Thread 0 picks the chunk by bisection, then each thread owns a CONTIGUOUS run of tokens of it.
+template <class Mass, class Weight>
+__device__ __forceinline__ int invert_running_sums(bool usable, float u, float denom, const float *s_cum, int nb, int chunk_size, int ncols, Mass mass, Weight weight) {
   __shared__ float s_wtot[4], s_wlast[4];
   __shared__ int s_wfirst[4];
-  __shared__ float s_denom, s_target;
+  __shared__ float s_target;
   __shared__ int s_sel;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nb = a.nblocks;
-  const size_t row = blockIdx.x;
-  const float *input = a.input + row * (size_t)a.ncols;
-  const float *bv = a.block_values + row * (size_t)nb, *bs = a.block_sums + row * (size_t)nb;
-  float *packed = a.packed_out + row * 2;
-  const float inv_t = a.inv_temperatures[row], u = a.uniforms[row];
-  float denom;
-  bool usable;
-  const float gmax = row_preamble<NT, true>(bv, bs, nb, inv_t, u, s_cum, denom, usable);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // ---- thread 0: the target, the chunk that holds it
   if (tid == 0) {
     int sel = -1;
@@ -557,7 +554,7 @@ __global__ void __launch_bounds__(NT) cat_stage2_kernel(CatArgs a) {
       } else {  // beyond the staged chunks: walk on
         float c = s_cum[nl - 1];
         for (int b = nl; b < nb; ++b) {
-          const float next = c + chunk_mass(bv, bs, b, inv_t, gmax);
+          const float next = c + mass(b);
           if (target < next) { sel = b; before = c; break; }
           c = next;
         }
@@ -566,23 +563,21 @@ __global__ void __launch_bounds__(NT) cat_stage2_kernel(CatArgs a) {
     }
     s_sel = sel;
     s_target = target;
-    s_denom = denom;
-    if (sel < 0) store_nan_row(packed, 2);
   }
   __syncthreads();
   const int sel = s_sel;
-  if (sel < 0) return;
+  if (sel < 0) return -1;
   const float target = s_target;
   // ---- the selected chunk: thread t owns the tokens [t * per, t * per + per)
-  const long long start = (long long)sel * a.chunk_size, left = (long long)a.ncols - start;
-  const int width = left < a.chunk_size ? (int)left : a.chunk_size;
-  const int per = (a.chunk_size + NT - 1) / NT, first = tid * per;
+  const long long start = (long long)sel * chunk_size, left = (long long)ncols - start;
+  const int width = left < chunk_size ? (int)left : chunk_size;
+  const int per = (chunk_size + NT - 1) / NT, first = tid * per;
   float w[MAXV], run[MAXV];  // weights, and their running sums inside the thread
   float acc = 0.0f;
 #pragma unroll
   for (int j = 0; j < MAXV; ++j) {
     const int local = first + j;
-    w[j] = (j < per && local < width) ? expf(input[start + local] * inv_t - gmax) : 0.0f;
+    w[j] = (j < per && local < width) ? weight(start + local) : 0.0f;
     acc += w[j];
     run[j] = acc;
   }
@@ -607,13 +602,32 @@ __global__ void __launch_bounds__(NT) cat_stage2_kernel(CatArgs a) {
   const float wave_last = wave_max((float)last);  // < 4096: exact in f32
   if (lane == 0) { s_wfirst[wave] = hits ? wave_first : -1; s_wlast[wave] = wave_last; }
   __syncthreads();
+  int token = -1;
   if (tid == 0) {
-    int token = -1;
     for (int i = 3; i >= 0; --i) if (s_wfirst[i] >= 0) token = s_wfirst[i];
     if (token < 0) token = (int)fmaxf(fmaxf(s_wlast[0], s_wlast[1]), fmaxf(s_wlast[2], s_wlast[3]));
-    if (token < 0) { store_nan_row(packed, 2); return; }  // unreachable while the chunk's mass is > 0
-    packed[0] = (float)(start + token);
-    packed[1] = input[start + token] * inv_t - gmax - logf(s_denom);
+    if (token >= 0) token += (int)start;  // otherwise unreachable while the chunk's mass is > 0
+  }
+  return token;
+}
+
+__global__ void __launch_bounds__(NT) cat_stage2_kernel(CatArgs a) {
+  __shared__ float s_cum[CAT_MAXB];  // chunk masses, then their running sums
+  const int tid = threadIdx.x, nb = a.nblocks;
+  const size_t row = blockIdx.x;
+  const float *input = a.input + row * (size_t)a.ncols;
+  const float *bv = a.block_values + row * (size_t)nb, *bs = a.block_sums + row * (size_t)nb;
+  float *packed = a.packed_out + row * 2;
+  const float inv_t = a.inv_temperatures[row], u = a.uniforms[row];
+  float denom;
+  bool usable;
+  const float gmax = row_preamble<NT, true>(bv, bs, nb, inv_t, u, s_cum, denom, usable);
+  const int token = invert_running_sums(usable, u, denom, s_cum, nb, a.chunk_size, a.ncols, [&](int b) { return chunk_mass(bv, bs, b, inv_t, gmax); },
+                                        [&](long long i) { return expf(input[i] * inv_t - gmax); });
+  if (tid == 0) {
+    if (token < 0) { store_nan_row(packed, 2); return; }
+    packed[0] = (float)token;
+    packed[1] = input[token] * inv_t - gmax - logf(denom);
   }
 }
 
@@ -834,6 +848,313 @@ static void run_nucleus(const float *input, const float *inv_temperatures, const
   hipLaunchKernelGGL(nuc_stage2_kernel, dim3(nrows), dim3(NUC_NT), 0, s, a2);
 }
 
+// ---------------------------------------------------------------- speculative decoding, the verifier: mrs_spec_verify_f32_batched (no reference symbol: the reference
+// runs the accept loop on the host over full-vocabulary probability vectors -- mistralrs-core/src/speculative/verifier.rs:44-115 greedy verification with a batched
+// device top-1, :200-290 the accept loop, :339-473 the stochastic rule).  Here the round of EVERY sequence is one launch group and nothing leaves the device but
+// (n_accepted, out_tokens).  Sequence s owns the rows seq_rows[s] .. seq_rows[s + 1] of target_logits: row i judges draft i, the last row is the bonus row.
+//   spec_stage1_kernel   grid (chunks, rows): the chunk in registers once (load_chunk); its greedy key (pack_max: largest value, lowest index, -0.0 == +0.0), its maximum
+//                        with the NaN flag (block_max_nan) and, in temperature mode, its share of the normaliser (chunk_softmax_share) for p -- cat_stage1_kernel's
+//                        values bit for bit -- and the same pair for q when the proposer handed over logits.                       (verifier.rs:44-115, 339-380)
+//   spec_decide_kernel   one workgroup per sequence walks the rows IN ORDER and stops at the first that ends the round, so later rows are never read (they may hold NaN).
+//                        greedy: winner == draft.  temperature: row_preamble for p (and q), p_d = w_p / denom_p, q_d likewise (1 without draft logits),
+//                        accept = q_d > 0 ? min(1, p_d / q_d) : (p_d > 0 ? 1 : 0), accepted iff u0 < accept.  All accepted: the bonus row is drawn here, by
+//                        row_preamble + invert_running_sums exactly as cat_stage2_kernel does at u1.  A rejection leaves a record for the two launches below.  (verifier.rs:200-290)
+//   spec_residual_kernel grid (chunks, sequences): only the workgroups of a sequence with a record stay; chunk mass of max(p - q, 0).              (verifier.rs:381-440)
+//   spec_resolve_kernel  one workgroup per sequence with a record: running residual sums in chunk order by thread 0, inversion at u1; a residual sum that is not positive
+//                        falls back to the draw from p.                                                                                           (verifier.rs:441-473)
+// No atomics and no float added in an order the hardware picks: the result is a function of the sequence's rows alone, whatever its neighbours in the launch are.
+struct SpecRec {  // left by spec_decide_kernel for a sequence whose round ends in a rejection
+  int32_t row;    // the rejected row (global index), -1: nothing left to do
+  int32_t draft, n_acc;
+  float gp, dp, gq, dq;  // gmax and denom of p and of q on that row
+  int32_t pad;
+};
+struct SpecArgs {
+  const float *target, *draft;  // draft == NULL: a deterministic proposer, q is one-hot on the draft
+  const int32_t *draft_ids, *seq_rows, *modes;
+  const float *inv_temperatures, *uniforms;
+  unsigned long long *keys;     // [rows][nb]
+  float *bvp, *bsp, *bvq, *bsq; // [rows][nb]
+  float *res;                   // [nseq][nb]
+  SpecRec *rec;                 // [nseq]
+  int32_t *n_accepted, *out_tokens;
+  int nseq, total_rows, ncols, chunk_size, nblocks;
+};
+constexpr int SPEC_MAX_ROWS = 8, SPEC_GREEDY = 0, SPEC_TEMPERATURE = 1;
+
+// (== ext_decode.hip pack_max, the key of mrs_sample_greedy_advance)
+__device__ __forceinline__ unsigned long long pack_max(float v, int idx) {
+  unsigned u = __float_as_uint(v);
+  u = u == 0x80000000u ? 0u : u;
+  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  return ((unsigned long long)u << 32) | (unsigned)(0x7fffffff - idx);
+}
+__device__ __forceinline__ int spec_seq_of_row(const int32_t *seq_rows, int nseq, int row) {  // the last s with seq_rows[s] <= row
+  int lo = 0, hi = nseq - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (seq_rows[mid] <= row) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+// max(p - q, 0) of one token; without draft logits q is one-hot on the draft, whose residual is 0 by definition (never p - 1 rounded)
+__device__ __forceinline__ float spec_residual(float xp, float xq, bool has_q, bool is_draft, float inv_t, const SpecRec &r) {
+  if (!has_q) return is_draft ? 0.0f : expf(xp * inv_t - r.gp) / r.dp;
+  return fmaxf(expf(xp * inv_t - r.gp) / r.dp - expf(xq * inv_t - r.gq) / r.dq, 0.0f);
+}
+
+__global__ void __launch_bounds__(NT) spec_stage1_kernel(SpecArgs a) {
+  __shared__ unsigned long long s_key[NT / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, chunk = blockIdx.x, row = blockIdx.y, nb = a.nblocks;
+  const int s = spec_seq_of_row(a.seq_rows, a.nseq, row);
+  const int mode = a.modes[s];
+  const float inv_t = a.inv_temperatures[s];
+  const long long start = (long long)chunk * a.chunk_size, left = (long long)a.ncols - start;
+  const int width = left <= 0 ? 0 : (left < a.chunk_size ? (int)left : a.chunk_size);
+  const size_t at = (size_t)row * nb + chunk;
+  float v[MAXV];
+  load_chunk(a.target + (size_t)row * a.ncols + start, width, v);
+  unsigned long long best = 0ull;
+  float m = -INFINITY;
+  bool nan = false, any_nan;
+#pragma unroll
+  for (int j = 0; j < MAXV; ++j) {
+    const int local = tid + j * NT;
+    if (local < width) {
+      const unsigned long long key = pack_max(v[j], (int)start + local);
+      best = key > best ? key : best;
+    }
+    if (v[j] != v[j]) nan = true;
+    else m = fmaxf(m, v[j]);
+  }
+  best = wave_max_u64(best);
+  if (lane == 0) s_key[wave] = best;
+  m = block_max_nan<NT / 64>(m, nan, any_nan);  // its barrier publishes s_key too
+  const float bvp = any_nan ? NAN : m;
+  if (tid == 0) {
+    unsigned long long k = s_key[0];
+    for (int i = 1; i < NT / 64; ++i) k = s_key[i] > k ? s_key[i] : k;
+    a.keys[at] = k;
+    a.bvp[at] = bvp;
+  }
+  if (mode != SPEC_TEMPERATURE) return;  // uniform over the workgroup
+  const float bsp = chunk_softmax_share(v, width, inv_t, bvp * inv_t, bvp == -INFINITY);  // two barriers: block_max_nan's slots are free again below
+  if (tid == 0) a.bsp[at] = bsp;
+  if (!a.draft) return;
+  load_chunk(a.draft + (size_t)row * a.ncols + start, width, v);
+  m = -INFINITY;
+  nan = false;
+#pragma unroll
+  for (int j = 0; j < MAXV; ++j) {
+    if (v[j] != v[j]) nan = true;
+    else m = fmaxf(m, v[j]);
+  }
+  m = block_max_nan<NT / 64>(m, nan, any_nan);
+  const float bvq = any_nan ? NAN : m;
+  const float bsq = chunk_softmax_share(v, width, inv_t, bvq * inv_t, bvq == -INFINITY);
+  if (tid == 0) { a.bvq[at] = bvq; a.bsq[at] = bsq; }
+}
+
+__device__ __forceinline__ void spec_store_round(const SpecArgs &a, int s, int n_acc, int cont) {  // thread 0: the entries past the continuation read -1; n_acc < 0: all of them
+  int32_t *out = a.out_tokens + (size_t)s * SPEC_MAX_ROWS;
+  for (int i = n_acc < 0 ? 0 : n_acc + 1; i < SPEC_MAX_ROWS; ++i) out[i] = -1;
+  if (n_acc >= 0) out[n_acc] = cont;
+  a.n_accepted[s] = n_acc < 0 ? -1 : n_acc;
+}
+
+__global__ void __launch_bounds__(NT) spec_decide_kernel(SpecArgs a) {
+  __shared__ float s_cum[CAT_MAXB];
+  __shared__ unsigned long long s_k[NT / 64];
+  __shared__ int s_n[NT / 64];
+  __shared__ int s_flag;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, s = blockIdx.x, nb = a.nblocks;
+  const int r0 = a.seq_rows[s], r1 = a.seq_rows[s + 1], n = r1 - r0 - 1, mode = a.modes[s];
+  int32_t *out = a.out_tokens + (size_t)s * SPEC_MAX_ROWS;
+  if (tid == 0) a.rec[s].row = -1;
+  if (r0 < 0 || r1 > a.total_rows || n < 0 || n >= SPEC_MAX_ROWS || (mode != SPEC_GREEDY && mode != SPEC_TEMPERATURE)) {
+    if (tid == 0) spec_store_round(a, s, -1, -1);
+    return;
+  }
+  int acc = 0;
+  if (mode == SPEC_GREEDY) {
+    int cont = -1;
+    for (int i = 0; i <= n && cont < 0; ++i) {
+      const size_t row = (size_t)(r0 + i);
+      unsigned long long best = 0ull;
+      bool nan = false;
+      for (int b = tid; b < nb; b += NT) {
+        const unsigned long long k = a.keys[row * nb + b];
+        const float c = a.bvp[row * nb + b];
+        best = k > best ? k : best;
+        if (c != c) nan = true;
+      }
+      best = wave_max_u64(best);
+      const bool wave_nan = __ballot(nan) != 0ull;
+      if (lane == 0) { s_k[wave] = best; s_n[wave] = wave_nan ? 1 : 0; }
+      __syncthreads();
+      unsigned long long k = 0ull;
+      int nans = 0;
+#pragma unroll
+      for (int w = 0; w < NT / 64; ++w) { k = s_k[w] > k ? s_k[w] : k; nans |= s_n[w]; }
+      __syncthreads();  // the slots are rewritten by the next row
+      if (nans) { acc = -1; break; }  // a NaN in a row that decides: unusable
+      const int winner = 0x7fffffff - (int)(k & 0xffffffffull);
+      if (i < n && winner == a.draft_ids[row]) {
+        if (tid == 0) out[i] = winner;
+        ++acc;
+      } else cont = winner;
+    }
+    if (tid == 0) spec_store_round(a, s, acc, cont);
+    return;
+  }
+  const float inv_t = a.inv_temperatures[s];
+  int state = 0;  // 0: every draft accepted, 1: a rejection (the record is written), 2: unusable
+  for (int i = 0; i < n && state == 0; ++i) {
+    const size_t row = (size_t)(r0 + i);
+    const float u0 = a.uniforms[2 * row];
+    float denom, gq = 0.0f, dq = 1.0f;
+    bool usable;
+    const float gp = row_preamble<NT, false>(a.bvp + row * nb, a.bsp + row * nb, nb, inv_t, u0, s_cum, denom, usable);
+    const float dp = denom;
+    bool ok = usable;
+    __syncthreads();  // thread 0 has left s_cum
+    if (a.draft) {
+      gq = row_preamble<NT, false>(a.bvq + row * nb, a.bsq + row * nb, nb, inv_t, u0, s_cum, denom, usable);
+      dq = denom;
+      ok = ok && usable;
+      __syncthreads();
+    }
+    if (tid == 0) {
+      const int d = a.draft_ids[row];
+      int flag = 2;
+      if (ok && d >= 0 && d < a.ncols) {
+        const float pd = expf(a.target[row * a.ncols + d] * inv_t - gp) / dp;
+        const float qd = a.draft ? expf(a.draft[row * a.ncols + d] * inv_t - gq) / dq : 1.0f;
+        const float accept = qd > 0.0f ? fminf(1.0f, pd / qd) : (pd > 0.0f ? 1.0f : 0.0f);
+        flag = u0 < accept ? 0 : 1;  // accept == 0 rejects u0 == 0 too
+        if (flag == 0) out[i] = d;
+        else a.rec[s] = SpecRec{(int32_t)row, d, i, gp, dp, gq, dq, 0};
+      }
+      s_flag = flag;
+    }
+    __syncthreads();
+    state = s_flag;
+    __syncthreads();
+    if (state == 0) ++acc;
+  }
+  if (state == 2) {
+    if (tid == 0) spec_store_round(a, s, -1, -1);
+    return;
+  }
+  if (state == 1) {  // the continuation comes from spec_resolve_kernel
+    if (tid == 0) spec_store_round(a, s, acc, -1);
+    return;
+  }
+  // every draft accepted (or none proposed): the bonus row is the categorical draw at u1, cat_stage2_kernel's arithmetic
+  const size_t row = (size_t)(r0 + n);
+  const float *input = a.target + row * a.ncols, *bv = a.bvp + row * nb, *bs = a.bsp + row * nb;
+  const float u1 = a.uniforms[2 * row + 1];
+  float denom;
+  bool usable;
+  const float gmax = row_preamble<NT, true>(bv, bs, nb, inv_t, u1, s_cum, denom, usable);
+  const int token = invert_running_sums(usable, u1, denom, s_cum, nb, a.chunk_size, a.ncols, [&](int b) { return chunk_mass(bv, bs, b, inv_t, gmax); },
+                                        [&](long long i) { return expf(input[i] * inv_t - gmax); });
+  if (tid == 0) spec_store_round(a, s, token < 0 ? -1 : acc, token);
+}
+
+__global__ void __launch_bounds__(NT) spec_residual_kernel(SpecArgs a) {
+  __shared__ float s_warp_sums[32];
+  const int tid = threadIdx.x, chunk = blockIdx.x, s = blockIdx.y;
+  const SpecRec r = a.rec[s];
+  if (r.row < 0) return;  // every sequence whose round did not end in a rejection leaves at once
+  const float inv_t = a.inv_temperatures[s];
+  const long long start = (long long)chunk * a.chunk_size, left = (long long)a.ncols - start;
+  const int width = left <= 0 ? 0 : (left < a.chunk_size ? (int)left : a.chunk_size);
+  float v[MAXV], vq[MAXV];
+  load_chunk(a.target + (size_t)r.row * a.ncols + start, width, v);
+  if (a.draft) load_chunk(a.draft + (size_t)r.row * a.ncols + start, width, vq);
+  float local_sum = 0.0f;
+#pragma unroll
+  for (int j = 0; j < MAXV; ++j) {
+    const int local = tid + j * NT;
+    if (local < width) local_sum += spec_residual(v[j], a.draft ? vq[j] : 0.0f, a.draft != nullptr, start + local == r.draft, inv_t, r);
+  }
+  const float mass = block_sum_ref_order(local_sum, s_warp_sums);
+  if (tid == 0) a.res[(size_t)s * a.nblocks + chunk] = mass;
+}
+
+__global__ void __launch_bounds__(NT) spec_resolve_kernel(SpecArgs a) {
+  __shared__ float s_cum[CAT_MAXB];
+  __shared__ float s_total;
+  __shared__ int s_residual;
+  const int tid = threadIdx.x, s = blockIdx.x, nb = a.nblocks;
+  const SpecRec r = a.rec[s];
+  if (r.row < 0) return;
+  const size_t row = (size_t)r.row;
+  const float inv_t = a.inv_temperatures[s], u1 = a.uniforms[2 * row + 1];
+  const float *res = a.res + (size_t)s * nb;
+  const float *input = a.target + row * a.ncols, *dinput = a.draft ? a.draft + row * a.ncols : nullptr;
+  for (int b = tid; b < nb && b < CAT_MAXB; b += NT) s_cum[b] = res[b];
+  __syncthreads();
+  if (tid == 0) {  // the residual masses in ascending chunk index, by one thread
+    float cum = 0.0f;
+    for (int b = 0; b < nb; ++b) {
+      cum += b < CAT_MAXB ? s_cum[b] : res[b];
+      if (b < CAT_MAXB) s_cum[b] = cum;
+    }
+    s_total = cum;
+    s_residual = cum > 0.0f && finite_f32(cum) ? 1 : 0;
+  }
+  __syncthreads();
+  int token;
+  if (s_residual) {
+    const float total = s_total;
+    token = invert_running_sums(u1 >= 0.0f && u1 < 1.0f, u1, total, s_cum, nb, a.chunk_size, a.ncols, [&](int b) { return res[b]; },
+                                [&](long long i) { return spec_residual(input[i], dinput ? dinput[i] : 0.0f, dinput != nullptr, i == r.draft, inv_t, r); });
+  } else {  // p <= q everywhere: draw from p
+    const float *bv = a.bvp + row * nb, *bs = a.bsp + row * nb;
+    float denom;
+    bool usable;
+    const float gmax = row_preamble<NT, true>(bv, bs, nb, inv_t, u1, s_cum, denom, usable);
+    token = invert_running_sums(usable, u1, denom, s_cum, nb, a.chunk_size, a.ncols, [&](int b) { return chunk_mass(bv, bs, b, inv_t, gmax); },
+                                [&](long long i) { return expf(input[i] * inv_t - gmax); });
+  }
+  if (tid == 0) spec_store_round(a, s, token < 0 ? -1 : r.n_acc, token);
+}
+
+static size_t spec_align(size_t x) { return (x + 255) & ~(size_t)255; }
+static size_t spec_workspace_bytes(int total_rows, int nseq, int nblocks) {
+  if (total_rows < 1 || nseq < 1 || nblocks < 1) return 0;
+  const size_t cells = (size_t)total_rows * nblocks;
+  return spec_align(cells * 8) + 4 * spec_align(cells * 4) + spec_align((size_t)nseq * nblocks * 4) + spec_align((size_t)nseq * sizeof(SpecRec));
+}
+static void run_spec_verify(const float *target, const float *draft, const int32_t *draft_ids, const int32_t *seq_rows, const int32_t *modes, const float *inv_temperatures,
+                            const float *uniforms, void *workspace, size_t workspace_bytes, int32_t *n_accepted, int32_t *out_tokens, int nseq, int total_rows, int ncols,
+                            int chunk_size, int nblocks, int64_t stream) {
+  // rows are a grid dimension; a sequence has 1..8 rows (the kernels check each sequence's own count on the device)
+  if (nseq < 1 || nseq > 65535 || total_rows < nseq || (long long)total_rows > (long long)SPEC_MAX_ROWS * nseq || total_rows > 65535) return;
+  if (!draw_shape_ok(total_rows, ncols, chunk_size, nblocks) || !workspace || workspace_bytes < spec_workspace_bytes(total_rows, nseq, nblocks)) return;
+  if ((uintptr_t)workspace & 7) return;
+  const size_t cells = (size_t)total_rows * nblocks;
+  char *w = (char *)workspace;
+  SpecArgs a{target, draft, draft_ids, seq_rows, modes, inv_temperatures, uniforms};
+  a.keys = (unsigned long long *)w; w += spec_align(cells * 8);
+  a.bvp = (float *)w; w += spec_align(cells * 4);
+  a.bsp = (float *)w; w += spec_align(cells * 4);
+  a.bvq = (float *)w; w += spec_align(cells * 4);
+  a.bsq = (float *)w; w += spec_align(cells * 4);
+  a.res = (float *)w; w += spec_align((size_t)nseq * nblocks * 4);
+  a.rec = (SpecRec *)w;
+  a.n_accepted = n_accepted; a.out_tokens = out_tokens;
+  a.nseq = nseq; a.total_rows = total_rows; a.ncols = ncols; a.chunk_size = chunk_size; a.nblocks = nblocks;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(spec_stage1_kernel, dim3(nblocks, total_rows), dim3(NT), 0, s, a);
+  hipLaunchKernelGGL(spec_decide_kernel, dim3(nseq), dim3(NT), 0, s, a);
+  hipLaunchKernelGGL(spec_residual_kernel, dim3(nblocks, nseq), dim3(NT), 0, s, a);
+  hipLaunchKernelGGL(spec_resolve_kernel, dim3(nseq), dim3(NT), 0, s, a);
+}
+
 // ---------------------------------------------------------------- logits pre-processing of the sampler (sort.cu:8-110; callers sampler.rs:1113-1169)
 // dst = x, then the listed tokens are updated in place: penalties (frequency / presence / repetition, counts from the context) or additive biases.
 __global__ void __launch_bounds__(NT) copy_f32_kernel(const float *__restrict__ x, float *__restrict__ dst, int n) {
@@ -987,6 +1308,13 @@ extern "C" void mrs_nucleus_large_f32_packed_batched(const float *input, const f
                                                      float *block_values, float *block_sums, float *packed_out, int nrows, int ncols, int chunk_size, int nblocks,
                                                      int64_t stream) {
   mrs::sampling::run_nucleus(input, inv_temperatures, uniforms, top_ps, min_ps, block_values, block_sums, packed_out, nrows, ncols, chunk_size, nblocks, stream);
+}
+extern "C" size_t mrs_spec_verify_workspace_bytes(int total_rows, int nseq, int nblocks) { return mrs::sampling::spec_workspace_bytes(total_rows, nseq, nblocks); }
+extern "C" void mrs_spec_verify_f32_batched(const float *target_logits, const float *draft_logits, const int32_t *draft_ids, const int32_t *seq_rows, const int32_t *modes,
+                                            const float *inv_temperatures, const float *uniforms, void *workspace, size_t workspace_bytes, int32_t *n_accepted,
+                                            int32_t *out_tokens, int nseq, int total_rows, int ncols, int chunk_size, int nblocks, int64_t stream) {
+  mrs::sampling::run_spec_verify(target_logits, draft_logits, draft_ids, seq_rows, modes, inv_temperatures, uniforms, workspace, workspace_bytes, n_accepted, out_tokens,
+                                 nseq, total_rows, ncols, chunk_size, nblocks, stream);
 }
 extern "C" void apply_sparse_penalties_f32(const void *x, void *dst, const uint32_t *token_ids, const float *counts, const int n, const int n_tokens,
                                            const float frequency_penalty, const float presence_penalty, const float repetition_penalty, int64_t stream) {

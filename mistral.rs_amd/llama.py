@@ -454,6 +454,61 @@ class Llama:
         self._chk(self._L.mrs_llama_forward_logits(self._h, b, self._stream()))
         return self.logits[:b]
 
+    # ---- speculative decoding (speculative.py): a verify step of ONE sequence, and the state advance after its round was judged
+    def set_state_seq(self, seq: int, token_id: int, position: int) -> None:
+        """`set_state` for one sequence `seq`: the other sequences' state stays as it is."""
+        cfg = self.cfg
+        if not 0 <= seq < cfg.max_batch or not 0 <= position < cfg.max_context_len:
+            raise ValueError("set_state_seq: sequence or position out of range")
+        blk = int(self.block_tables[seq, position // cfg.block_size].item())
+        self.input_ids[seq] = int(token_id)
+        self.positions[seq] = int(position)
+        self.context_lens[seq] = int(position) + 1
+        self.slot_mapping[seq] = blk * cfg.block_size + position % cfg.block_size
+        self._replays_left = None
+        self._need_embed = True
+
+    @property
+    def verify_ids_ptr(self) -> int:
+        """device address of the verify step's token ids, int32 [9]: [0] the anchor (filled by the step), [1..7] the caller's drafts, [8] spare -- so that the
+        address + 4 is a whole draft_ids [8] for `SpecVerify` (the bonus row's entry, which nobody reads, still lies inside the buffer)"""
+        self._L.mrs_llama_verify_ids.restype = C.c_void_p
+        self._L.mrs_llama_verify_ids.argtypes = [C.c_void_p]
+        return int(self._L.mrs_llama_verify_ids(self._h))
+
+    def verify_step(self, seq: int, n_rows: int, drafts=None) -> torch.Tensor:
+        """n_rows <= min(8, max_batch) rows of sequence `seq` in one step of the batched decode launches (mrs_llama_verify_step, decode engine only): the anchor token
+        (input_ids[seq] at positions[seq]) and n_rows - 1 drafts at the following positions, every row attending to [0, its position].  `drafts`: the n_rows - 1 ids
+        (uploaded here), or None when the caller wrote them to `verify_ids_ptr` itself.  Returns logits[:n_rows]; K/V of all rows are in the sequence's pages, the decode
+        state and the other sequences' block-table rows are untouched."""
+        self._set_mode()
+        self._need_embed = True
+        if not 1 <= int(n_rows) <= min(8, self.cfg.max_batch):
+            raise ValueError(f"verify_step: {n_rows} rows, at most min(8, max_batch = {self.cfg.max_batch})")
+        if drafts is not None:
+            d = np.asarray(list(drafts), dtype=np.int32).reshape(-1)
+            if d.size != n_rows - 1:
+                raise ValueError(f"verify_step: {n_rows} rows need {n_rows - 1} drafts, got {d.size}")
+            if d.size:
+                if getattr(self, "_verify_ids", None) is None:  # the runner's id buffer lies inside the workspace tensor: a view of it
+                    off = self.verify_ids_ptr - self.workspace.data_ptr()
+                    self._verify_ids = self.workspace[off:off + 36].view(torch.int32)  # int32 [9]
+                self._verify_ids[1:1 + d.size].copy_(torch.from_numpy(d))
+        self._L.mrs_llama_verify_step.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        self._chk(self._L.mrs_llama_verify_step(self._h, int(seq), int(n_rows), self._stream()))
+        return self.logits[:n_rows]
+
+    def spec_advance(self, n_accepted: torch.Tensor, out_tokens: torch.Tensor, seq: int = 0) -> None:
+        """After `SpecVerify` judged a round of sequence `seq` (n_accepted [1], out_tokens [8] on the device): append the emitted tokens to tokens_out at step_counter and
+        point the decode state at the continuation token (mrs_spec_advance) -- no host work, nothing read back."""
+        cfg = self.cfg
+        self._L.mrs_spec_advance.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_void_p]
+        self._chk(self._L.mrs_spec_advance(n_accepted.data_ptr(), out_tokens.data_ptr(), int(seq), self.input_ids.data_ptr(), self.tokens_out.data_ptr(),
+                                           self.tokens_out.shape[1], self.step_counter.data_ptr(), self.positions.data_ptr(), self.context_lens.data_ptr(),
+                                           self.slot_mapping.data_ptr(), self.block_tables.data_ptr(), cfg.max_blocks_per_seq, cfg.block_size, self._stream()))
+        self._replays_left = None
+        self._need_embed = True
+
     def decode_step(self, b: int = 1) -> None:
         self._set_mode()
         self._need_embed = True
