@@ -1048,8 +1048,8 @@ class Llama {
 
   // ---- speculative decoding, the verify step: n_rows rows of sequence `seq` (its anchor token + the drafts in ws.verify_ids[1..]) at consecutive positions through the
   //      batched engine launches.  One small launch gathers the rows' inputs next to the decode state (ws.verify_*, a verify-only block table); forward_engine then reads
-  //      THEM instead of bufs: no other sequence's block-table row is touched and nothing is saved or restored.  Nothing here allocates or synchronises, but capturing
-  //      the step in a graph is untested.  Leaves logits[:n_rows].
+  //      THEM instead of bufs: no other sequence's block-table row is touched and nothing is saved or restored.  Nothing here allocates or synchronises: a greedy round
+  //      (this step, the verifier, mrs_spec_advance) captured in a graph replays with the eager bits (tests/test_speculative.py).  Leaves logits[:n_rows].
   int verify_step(int seq, int n_rows, hipStream_t s) const {
     if (check_ready(1)) return -1;
     if (cfg.use_fused != 2 || !engine_ok()) return fail("verify step: needs the decode engine (use_fused = 2 and a decode-layout copy of every linear)");

@@ -1,10 +1,13 @@
 """Speculative decoding on the runner (mistralrs_amd/speculative.py): greedy rounds are LOSSLESS -- the ids and the logits bits of a plain `decode_step` run, whatever the
-proposer does -- because the batched decode launches of the verify step produce the batch-1 step's bits.  Smallest engine model of tests/test_dec_model.py (2 layers,
-Q4_K / Q6_K)."""
+proposer does -- because the batched decode launches of the verify step produce the batch-1 step's bits; that holds on a sequence other than 0 with decoding neighbours;
+without drafts a run at a temperature draws the tokens of `sampler.generate(top_k=0)`; sampled rounds with rejections are judged round by round against float64; one
+greedy round replays as a captured graph.  Smallest engine model of tests/test_dec_model.py (2 layers, Q4_K / Q6_K)."""
 import numpy as np
 import pytest
 
+from tests.test_categorical import MAX_AMBIGUOUS
 from tests.test_dec_model import Q4KM, _mk
+from tests.test_spec_verify import _ambiguous_share, _exact_rule, _p_of
 
 pytestmark = pytest.mark.gpu
 NEW = 48
@@ -156,3 +159,291 @@ def test_isolation_and_refusals(pair):
         speculative.generate_speculative(m, prompt, 4, rp, 8)
     with pytest.raises(ValueError):
         m.verify_step(0, 9, [0] * 8)
+
+
+# ---------------------------------------------------------------- a sequence other than 0
+def _seq_state(m, n):
+    return [t[:n].clone() for t in (m.input_ids, m.positions, m.context_lens, m.slot_mapping)]
+
+
+def test_speculative_rounds_on_another_sequence(oracle, dev):
+    """Sequences 0, 1 and 2 hold other prompts and a decode state; sequence 3 runs speculative rounds (7 drafts, planted errors, the first round's rows at positions
+    28 .. 35) from a loop of set_state_seq / verify_step / SpecVerify / spec_advance: ids, logits bits and pages are those of a plain run on sequence 0 of a second model,
+    and nothing of sequences 0 .. 2 nor any block-table entry changes.  Then a draft model on sequence 2 proposes what its twin on sequence 0 proposes."""
+    import torch
+    from mistralrs_amd import speculative
+    SEQ = 3
+    n_prompt, new, k_max, lens = 29, 40, 7, (20, 33, 7)
+    cfg, _, m_plain, _, _ = _mk(oracle, dev, Q4KM(oracle), "bf16", max_batch=8)
+    _, _, m, _, _ = _mk(oracle, dev, Q4KM(oracle), "bf16", max_batch=8)
+    assert m.prefill_is_exact  # the prompt path leaves the decode steps' pages: what the comparison of pages below relies on
+    prompt = _prompt(cfg, n_prompt)
+    plain, rows = _plain(m_plain, prompt, new)
+    others = [[(3 + s + (5 + 2 * s) * i) % cfg.vocab_size for i in range(n + 1)] for s, n in enumerate(lens)]
+    for s, o in enumerate(others):
+        m.prefill(o[:-1], 0, seq=s)
+        m.set_state_seq(s, o[-1], len(o) - 1)
+    m.prefill(prompt[:-1], 0, seq=SEQ)
+    m.tokens_out.fill_(-7)
+    m.step_counter.zero_()
+    m.set_state_seq(SEQ, prompt[-1], len(prompt) - 1)
+    before_state, before_bt = _seq_state(m, SEQ), m.block_tables.clone()
+    before_pages = [_pages(m, n, seq=s) for s, n in enumerate(lens)]
+    assert len({int(v) for v in m.block_tables[:SEQ + 1, :2].reshape(-1).cpu()}) == 2 * (SEQ + 1)  # the sequences' table rows differ: a wrong row shows
+    verify = speculative.SpecVerify(cfg.vocab_size, m.device)
+    rp = Replay(plain, cfg.vocab_size, wrong=lambda j: j % 5 == 4)
+    rp.reset()
+    toks, got_rows, rounds = [], [], 0
+    while len(toks) < new:
+        drafts, _ = rp.propose(prompt + toks, min(k_max, new - len(toks) - 1), n_generated=len(toks))
+        logits = m.verify_step(SEQ, len(drafts) + 1, drafts)
+        verify(logits, m.verify_ids_ptr + 4, [0, len(drafts) + 1])
+        m.spec_advance(verify.n_accepted, verify.out_tokens, SEQ)
+        res = verify.result.cpu().numpy()
+        n_acc = int(res[0])
+        assert 0 <= n_acc <= len(drafts)
+        got_rows += logits[:n_acc + 1].clone().unbind(0)
+        toks += [int(t) for t in res[1:2 + n_acc]]
+        rounds += 1
+        # the decode state of the sequence after the round: the continuation token at the next position, its slot from ITS table row
+        pos = len(prompt) - 1 + len(toks)
+        assert int(m.input_ids[SEQ]) == toks[-1] and int(m.positions[SEQ]) == pos and int(m.context_lens[SEQ]) == pos + 1
+        assert int(m.slot_mapping[SEQ]) == int(m.block_tables[SEQ, pos // cfg.block_size]) * cfg.block_size + pos % cfg.block_size
+    assert toks == plain and rounds < new, (toks, plain)
+    for i, (a, b) in enumerate(zip(got_rows, rows)):
+        assert torch.equal(a.view(torch.int32), b.view(torch.int32)), f"token {i}: the logits row differs from the plain run's"
+    length = len(prompt) + len(toks) - 1
+    assert length > 32 and len(prompt) - 1 < 31  # the first round's rows straddled positions 31 | 32
+    for a, b in zip(_pages(m, length, seq=SEQ), _pages(m_plain, length)):
+        assert torch.equal(a, b), "K/V pages of the sequence differ from the plain run's"
+    assert int(m.step_counter.item()) == len(toks) and m.tokens_out[SEQ, :len(toks)].cpu().numpy().tolist() == toks
+    assert bool((m.tokens_out[:SEQ] == -7).all()) and bool((m.tokens_out[SEQ + 1:] == -7).all())
+    assert all(torch.equal(a, b) for a, b in zip(before_state, _seq_state(m, SEQ))), "the decode state of sequences 0 .. 2 changed"
+    assert torch.equal(m.block_tables, before_bt)
+    for s, n in enumerate(lens):
+        assert all(torch.equal(a, b) for a, b in zip(before_pages[s], _pages(m, n, seq=s))), f"pages of sequence {s} changed"
+    # a draft model on sequence 2 against its twin (same weights) on sequence 0: same ids, same logits rows.  The comparisons above are done: the two models'
+    # pages are free.  The twin on sequence 0 takes its long gaps through the prompt path, the one on sequence 2 through 8-row steps.
+    p0, p2 = speculative.DraftModelProposer(m_plain, seq=0), speculative.DraftModelProposer(m, seq=2)
+    ctx, k = list(prompt), 3
+    for temperature, seed in ((0.0, 0), (0.8, 3), (0.0, 0), (0.8, 4)):
+        ids0, rows0 = p0.propose(ctx, k, temperature, seed, len(ctx) - len(prompt))
+        ids2, rows2 = p2.propose(ctx, k, temperature, seed, len(ctx) - len(prompt))
+        assert ids0 == ids2 and len(ids0) == k and rows0.shape == rows2.shape == (k + 1, cfg.vocab_size)
+        assert torch.equal(rows0[:k].view(torch.int32), rows2[:k].view(torch.int32)) and p0.done == p2.done
+        ctx = ctx + ids0[:k - 1] + [(ids0[k - 1] + 1) % cfg.vocab_size]  # the last draft "rejected": the next proposal starts from another token
+    assert torch.equal(m.block_tables, before_bt)
+
+
+# ---------------------------------------------------------------- at a temperature
+TEMPERATURE = 0.8
+
+
+@pytest.fixture(scope="module")
+def sampled(oracle, dev):
+    """a target, a second model with the target's weights for the plain sampled run, and a draft model with OTHER weights; the greedy plain run of the prompt"""
+    cfg, _, m, _, _ = _mk(oracle, dev, Q4KM(oracle), "bf16", max_batch=8)
+    _, _, m2, _, _ = _mk(oracle, dev, Q4KM(oracle), "bf16", max_batch=8)
+    _, _, md, _, _ = _mk(oracle, dev, Q4KM(oracle), "bf16", max_batch=8, seed=1)
+    prompt, new = _prompt(cfg), 32
+    greedy, _ = _plain(m2, prompt, new)
+    return cfg, m, m2, md, prompt, greedy, new
+
+
+@pytest.mark.parametrize("seed", [5, 6])
+def test_no_drafts_at_a_temperature_is_the_plain_sampled_run(sampled, seed):
+    """the module docstring of speculative.py: without drafts a run draws the tokens of `sampler.generate(top_k=0)` -- u1 of token t is uniform_for(seed, t) in both.
+    `sampler.generate` takes the first row from the prompt path (the whole prompt through `prefill`), the speculative run from a one-row verify step after the prompt
+    path handled prompt[:-1]: the same bits only where the prompt path runs in the decode engine's arithmetic (`prefill_is_exact`), which this model kind does."""
+    from mistralrs_amd import sampler, speculative
+    cfg, m, m2, md, prompt, greedy, new = sampled
+    assert m.prefill_is_exact and m2.prefill_is_exact
+    toks, st = speculative.generate_speculative(m, prompt, new, Replay(greedy, cfg.vocab_size), 0, temperature=TEMPERATURE, seed=seed)
+    want, _ = sampler.generate(m2, prompt, new, top_k=0, temperature=TEMPERATURE, seed=seed)
+    assert toks == want and len(toks) == new and st["rounds"] == new and st["proposed"] == 0
+    assert toks != greedy
+
+
+class Recording:
+    """a proposer that keeps what the wrapped one handed over: (n_generated, drafts, a clone of the draft rows or None) per call"""
+
+    def __init__(self, inner):
+        self.inner, self.calls = inner, []
+
+    def reset(self):
+        self.inner.reset()
+        self.calls = []
+
+    def propose(self, context, k_max, temperature=0.0, seed=0, n_generated=0):
+        ids, rows = self.inner.propose(context, k_max, temperature, seed, n_generated)
+        self.calls.append((int(n_generated), [int(t) for t in ids], None if rows is None else rows.clone()))
+        return ids, rows
+
+
+def _judge_rounds(cfg, toks, st, calls, seed):
+    """Every round of a sampled run against the float64 rule, from the round's OWN rows: the device's target rows (st["logits"]) and the recorded draft rows (one-hot q
+    without them).  A draft model's own draws are judged too: draft i of the round that starts at token t0 is the token whose float64 interval of softmax(q row i / T)
+    holds uniform_for(seed, DRAFT_STREAM + t0 + i) -- every draft, judged by the verifier or not.
+    Returns (judged decisions, ambiguous ones by the float64 reference alone, rounds that ended in a rejection, accepted drafts)."""
+    from mistralrs_amd.sampler import CHUNK_SIZE, uniform_for
+    from mistralrs_amd.speculative import DRAFT_STREAM, U0_STREAM
+    inv_t = np.float32(1.0 / TEMPERATURE)
+    eps = (-(-cfg.vocab_size // CHUNK_SIZE) + 32) * 2.0 ** -23
+    calls = list(calls)
+    if st["rounds"] == len(calls) + 1:  # one token was left: the last round had no room for a draft and the proposer was not asked
+        calls.append((len(toks) - 1, [], None))
+    assert st["rounds"] == len(calls)
+    ends = [c[0] for c in calls[1:]] + [len(toks)]
+    judged = excused = rejected = accepted = 0
+    for (t0, drafts, qrows), t1 in zip(calls, ends):
+        emitted, rows = toks[t0:t1], [r.cpu().numpy() for r in st["logits"][t0:t1]]
+        n_acc, k = len(emitted) - 1, len(drafts)
+        assert 0 <= n_acc <= k and emitted[:n_acc] == drafts[:n_acc], (t0, emitted, drafts)
+        assert qrows is None or qrows.shape[0] == k + 1
+        for i in range(k if qrows is not None else 0):  # the third stream: the draft model's draw of draft i
+            ud = np.array([uniform_for(seed, DRAFT_STREAM + t0 + i)], np.float64)
+            te, clear = _ambiguous_share(np.cumsum(_p_of(qrows[i].cpu().numpy(), inv_t)), ud, eps)
+            judged += 1
+            if clear[0]:
+                assert drafts[i] == te[0], f"draft of token {t0 + i}: the proposer drew {drafts[i]}, the exact interval at u = {ud[0]} is token {te[0]}'s"
+            else:
+                excused += 1
+        cdf = None
+        for i in range(min(n_acc + 1, k)):  # the accepted drafts and the first rejected one
+            d = drafts[i]
+            if qrows is None:  # q is one-hot on the draft: accept = p_d, the residual is p without the draft
+                p = _p_of(rows[i], inv_t)
+                accept, res = p[d], p.copy()
+                res[d] = 0.0
+                cdf = np.cumsum(res) / res.sum()
+            else:
+                accept, cdf = _exact_rule(rows[i], qrows[i].cpu().numpy(), d, inv_t)
+            u0 = float(uniform_for(seed, U0_STREAM + t0 + i))
+            judged += 1
+            if abs(u0 - accept) <= eps:
+                excused += 1
+            elif i < n_acc:
+                assert u0 < accept, f"token {t0 + i}: draft accepted at u0 = {u0} >= accept = {accept}"
+            else:
+                assert u0 >= accept, f"token {t0 + i}: draft rejected at u0 = {u0} < accept = {accept}"
+        if n_acc == k:  # every draft accepted (or none made): the bonus row's own distribution
+            cdf = np.cumsum(_p_of(rows[k], inv_t))
+        else:
+            rejected += 1
+        accepted += n_acc
+        u1 = np.array([uniform_for(seed, t0 + n_acc)], np.float64)
+        te, clear = _ambiguous_share(cdf, u1, eps)
+        judged += 1
+        if clear[0]:
+            assert emitted[-1] == te[0], f"token {t0 + n_acc}: drew {emitted[-1]}, the exact interval at u1 = {u1[0]} is token {te[0]}'s"
+        else:
+            excused += 1
+    assert accepted == st["accepted"]
+    return judged, excused, rejected, accepted
+
+
+# seeds for which the float64 reference alone leaves no more than MAX_AMBIGUOUS of a run's decisions ambiguous and the run has both outcomes.  Observed on the MI355X
+# (ambiguous / judged decisions; the draft model's count includes its own draws):
+#   replay      seed 63: 0 / 61  (30 rounds, 29 ended in a rejection,  2 of 112 drafts accepted)      seed 50: 0 / 62  (31 rounds, 30 rejections,  1 of 114 accepted)
+#   draft_model seed 12: 1 / 136 (23 rounds, 22 ended in a rejection,  9 of  82 drafts accepted)      seed 15: 1 / 116 (18 rounds, 17 rejections, 14 of  67 accepted)
+# The model's distributions are flat and the replay's accept probability is p_draft: of seeds 0 .. 119 fourteen accept a draft at all, seed 63 alone accepts two.
+SAMPLED_SEEDS = [("replay", 63), ("replay", 50), ("draft_model", 12), ("draft_model", 15)]
+
+
+@pytest.mark.parametrize("kind,seed", SAMPLED_SEEDS, ids=[f"{k}-{s}" for k, s in SAMPLED_SEEDS])
+def test_sampled_rounds_follow_the_rule(sampled, kind, seed):
+    """temperature 0.8 with rejections: `replay` drafts the greedy run's tokens with planted errors and hands over no logits (q one-hot); `draft_model` is a model with
+    OTHER weights (p != q).  What generate_speculative hands the verifier and the proposer -- the three uniform streams, the draft ids' address, the draft rows'
+    alignment -- decides every round's outcome, so each round is recomputed in float64 from the device's own target rows and the recorded draft rows."""
+    import torch
+    from mistralrs_amd import speculative
+    cfg, m, m2, md, prompt, greedy, new = sampled
+    n_draft = 4
+    inner = Replay(greedy, cfg.vocab_size, wrong=lambda j: j % 4 == 3) if kind == "replay" else speculative.DraftModelProposer(md)
+    rec = Recording(inner)
+    toks, st = speculative.generate_speculative(m, prompt, new, rec, n_draft, temperature=TEMPERATURE, seed=seed, return_logits=True)
+    calls = rec.calls
+    assert len(toks) == new == len(st["logits"]) and st["accepted"] + st["rounds"] == len(toks) and st["accepted"] <= st["proposed"]
+    assert all((rows is None) == (kind == "replay") for _, _, rows in calls)
+    judged, excused, rejected, accepted = _judge_rounds(cfg, toks, st, calls, seed)
+    print(f"{kind} seed {seed}: {st['rounds']} rounds, {rejected} ended in a rejection, {accepted} of {st['proposed']} drafts accepted; ambiguous {excused} of {judged} decisions")
+    assert excused <= MAX_AMBIGUOUS * judged, "the float64 rule alone leaves too many decisions ambiguous: pick another seed"
+    assert rejected >= 1 and accepted >= 1, "the run proves nothing: pick another seed"
+    toks2, st2 = speculative.generate_speculative(m, prompt, new, rec, n_draft, temperature=TEMPERATURE, seed=seed, return_logits=True)
+    assert toks2 == toks and {k: v for k, v in st2.items() if k != "logits"} == {k: v for k, v in st.items() if k != "logits"}
+    assert all(torch.equal(a.view(torch.int32), b.view(torch.int32)) for a, b in zip(st["logits"], st2["logits"]))
+    assert [c[:2] for c in rec.calls] == [c[:2] for c in calls]
+
+
+# ---------------------------------------------------------------- one round as a captured graph
+def test_greedy_round_replays_as_a_captured_graph(pair):
+    """A greedy round of 4 rows is three launches that allocate and synchronise nowhere: the verify step (drafts already in the runner's id buffer), the verifier with its
+    small arrays uploaded beforehand, the state advance.  Captured once and replayed for 8 rounds with Replay drafts (every fourth one wrong), it emits the ids, the logits
+    bits and the pages of the same rounds run eagerly, which are the plain run's."""
+    import ctypes as C
+    import torch
+    from mistralrs_amd import _lib, speculative
+    from mistralrs_amd.sampler import CHUNK_SIZE
+    cfg, m_plain, m, prompt, plain, rows = pair
+    dev, vocab, K, ROUNDS = m.device, cfg.vocab_size, 3, 8
+    verify = speculative.SpecVerify(vocab, dev)
+    vp, i, ll, sz = C.c_void_p, C.c_int, C.c_int64, C.c_size_t
+    launch = _lib.sym("core", "mrs_spec_verify_f32_batched", [vp] * 8 + [sz, vp, vp, i, i, i, i, i, ll])
+    ints = torch.tensor([0, K + 1, speculative.GREEDY], dtype=torch.int32, device=dev)  # seq_rows [2], modes [1]
+    floats = torch.tensor([1.0] + [0.0] * (2 * (K + 1)), dtype=torch.float32, device=dev)  # inverse temperature [1], uniforms [rows][2] (greedy reads neither)
+    ws = (verify.workspace.data_ptr() + 7) & ~7
+    off = m.verify_ids_ptr - m.workspace.data_ptr()
+    ids_buf = m.workspace[off:off + 36].view(torch.int32)  # the runner's id buffer: [0] the anchor, [1..7] the drafts
+
+    def one_round():
+        logits = m.verify_step(0, K + 1, None)
+        launch(logits.data_ptr(), None, m.verify_ids_ptr + 4, ints.data_ptr(), ints.data_ptr() + 8, floats.data_ptr(), floats.data_ptr() + 4, ws,
+               verify.workspace.numel() - 8, verify.n_accepted.data_ptr(), verify.out_tokens.data_ptr(), 1, K + 1, vocab, CHUNK_SIZE, verify.nblocks,
+               torch.cuda.current_stream().cuda_stream)
+        m.spec_advance(verify.n_accepted, verify.out_tokens, 0)
+        return logits
+
+    def start():
+        m.prefill(prompt[:-1], 0)
+        m.set_state([prompt[-1]], [len(prompt) - 1])
+        m.step_counter.zero_()
+
+    def run(step):
+        rp = Replay(plain, vocab, wrong=lambda j: j % 4 == 3)
+        rp.reset()
+        toks, out = [], []
+        for _ in range(ROUNDS):
+            drafts = torch.tensor(rp.propose(prompt + toks, K, n_generated=len(toks))[0], dtype=torch.int32, device=dev)
+            assert drafts.numel() == K
+            ids_buf[1:1 + K].copy_(drafts)  # a device copy ahead of the round
+            logits = step()
+            res = verify.result.cpu().numpy()
+            n_acc = int(res[0])
+            assert 0 <= n_acc <= K
+            out += logits[:n_acc + 1].clone().unbind(0)
+            toks += [int(t) for t in res[1:2 + n_acc]]
+        return toks, out, _pages(m, len(prompt) + len(toks) - 1)
+
+    assert m.prefill_is_exact
+    start()
+    eager = run(one_round)  # also the warm-up: every kernel of the round has run before the capture
+    assert ROUNDS < len(eager[0]) < ROUNDS * (K + 1) and eager[0] == plain[:len(eager[0])]
+    start()
+    saved = [t.clone() for t in (m.input_ids, m.positions, m.context_lens, m.slot_mapping, m.step_counter, m.tokens_out)]
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        graph_logits = one_round()
+    for t, v in zip((m.input_ids, m.positions, m.context_lens, m.slot_mapping, m.step_counter, m.tokens_out), saved):
+        t.copy_(v)
+
+    def replay():
+        g.replay()
+        return graph_logits
+
+    replayed = run(replay)
+    assert replayed[0] == eager[0], (replayed[0], eager[0])
+    for j, (a, b, c) in enumerate(zip(replayed[1], eager[1], rows)):
+        assert torch.equal(a.view(torch.int32), b.view(torch.int32)) and torch.equal(a.view(torch.int32), c.view(torch.int32)), f"token {j}: logits rows differ"
+    for a, b, c in zip(replayed[2], eager[2], _pages(m_plain, len(prompt) + len(eager[0]) - 1)):
+        assert torch.equal(a, b) and torch.equal(a, c), "K/V pages differ"
+    assert int(m.step_counter.item()) == len(eager[0]) and m.tokens_out[0, :len(eager[0])].cpu().numpy().tolist() == eager[0]
