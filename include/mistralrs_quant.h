@@ -196,6 +196,34 @@ void launch_pack_3bit_kernel(const uint32_t *d_input, int32_t *d_output, size_t 
 void launch_pack_4bit_kernel(const uint8_t *d_input, uint8_t *d_output, size_t num_input_elements, size_t input_width, void *stream);
 void launch_pack_8bit_kernel(const uint8_t *d_input, uint8_t *d_output, size_t num_elements, void *stream);
 
+/* ---- MXFP4 (GPT-OSS): out = input . W^T (+ bias) straight from the packed tensor.  weight [N][K/2] u8, two E2M1 values per byte (low nibble =
+ *      element k, high nibble = k + 1; magnitudes {0, .5, 1, 1.5, 2, 3, 4, 6}, bit 3 = sign); weight_scale [N][K/32] u8 E8M0, scale byte s means
+ *      f32_from_bits(s << 23) (s = 0 -> 0.0; s = 255 is outside the contract); K % 32 == 0.  Products exact in f32, f32 accumulation, bias added in
+ *      f32 after the K sum, one rounding to the output type.  MoE: weights [E][N][K/2], weight_scales [E][N][K/32], biases [E][N], indices
+ *      [num_tokens][topk] u32, output [num_tokens][topk][N]; input [num_tokens][K] (every slot of a token reads the same row) or, with
+ *      input_has_topk_dim, [num_tokens][topk][K]; an expert id >= num_experts reads nothing and leaves its output row untouched.  The indexed and the
+ *      grouped entry points compute the same result for any num_tokens (the reference takes the grouped one when num_tokens > 1, ops.rs:380-400).
+ *      The *_wmma_* entry points of ffi.rs:33-57,129-161 are gated behind has_mxfp4_wmma_kernels there and are not part of this library.
+ *      replaces kernels/mxfp4/mxfp4_gemm.cu ; Rust: src/mxfp4/ffi.rs:7-31,59-127 ; callers mxfp4/ops.rs:16-214 (mxfp4_matmul), :313-614
+ *      (mxfp4_indexed_moe_gemm) <- MXFP4Layer::forward_raw / gather_forward_raw (mxfp4/mod.rs:106-182) */
+void launch_mxfp4_matmul_f16(const void *input, const uint8_t *weight, const uint8_t *weight_scale, const void *bias, void *output, int M, int N, int K,
+                             bool has_bias, void *stream);
+void launch_mxfp4_matmul_bf16(const void *input, const uint8_t *weight, const uint8_t *weight_scale, const void *bias, void *output, int M, int N, int K,
+                              bool has_bias, void *stream);
+void launch_mxfp4_indexed_moe_gemm_f16(const void *input, const uint8_t *weights, const uint8_t *weight_scales, const void *biases, const uint32_t *indices,
+                                       void *output, int num_tokens, int topk, int num_experts, int N, int K, bool has_bias, bool input_has_topk_dim, void *stream);
+void launch_mxfp4_indexed_moe_gemm_bf16(const void *input, const uint8_t *weights, const uint8_t *weight_scales, const void *biases, const uint32_t *indices,
+                                        void *output, int num_tokens, int topk, int num_experts, int N, int K, bool has_bias, bool input_has_topk_dim, void *stream);
+void launch_mxfp4_moe_grouped_gemm_f16(const void *input, const uint8_t *weights, const uint8_t *weight_scales, const void *biases, const uint32_t *indices,
+                                       void *output, int num_tokens, int topk, int num_experts, int N, int K, bool has_bias, bool input_has_topk_dim, void *stream);
+void launch_mxfp4_moe_grouped_gemm_bf16(const void *input, const uint8_t *weights, const uint8_t *weight_scales, const void *biases, const uint32_t *indices,
+                                        void *output, int num_tokens, int topk, int num_experts, int N, int K, bool has_bias, bool input_has_topk_dim, void *stream);
+/*      LDS bytes one workgroup may use on the current device (the device attribute; mxfp4/ffi.rs:93, caller ops.rs:379) */
+int mxfp4_get_max_smem_optin(void);
+/* MI355X-native addition (not in the reference ABI): the route of the last mxfp4 launch of this process -- 1 streaming GEMV (M <= 8), 2 bf16 MFMA tile,
+ * 3 per-slot MoE GEMV, 4 grouped MoE tile, 5 f16 dense in GEMV chunks of 8 rows; see csrc/mxfp4.hip */
+int mxfp4_last_route(void);
+
 /* MI355X-native addition (not in the reference ABI): tile policy of the int8-MFMA MMQ kernels, see csrc/mmq.hip */
 void mrs_mmq_set_small_tiles_below(int n);
 

@@ -140,6 +140,10 @@ int mrs_dec_mm_qkv(const void *qi_q, int type_q, int nq, const void *qi_k, int t
  * dequantize_w(); the dequantized values are bit-identical to dequantize_{4,8}bit_u8_kernel_*.  -1 = outside the fused kernel (keep dequantize + dense matmul). */
 int mrs_hqq_gemv(int bits, int dtype, const void *wq, const void *scale, const void *zero, const void *bias, const void *x, int ldx, void *out, int ldo,
                  int N, int K, int b, void *stream);
+/* MXFP4 rows -> f32 / f16 / bf16 (ext_mxfp4.hip): out row r [K] = the dequantized row ids[r] (r when ids is null) of blocks [*][K/2] / scales [*][K/32]; the f32
+ * value table[nibble] * f32_from_bits(scale << 23) is exact and converted once.  out_dtype 0 = f32, 1 = f16, 2 = bf16.  Role: MXFP4Layer::dequantize_w and
+ * embedding_forward_raw (mxfp4/mod.rs:87-103,615-707), both CPU loops in the reference.  0 on success, < 0 for arguments outside the kernel. */
+int mrs_mxfp4_dequantize_rows(const void *blocks, const void *scales, const int32_t *ids, int64_t rows, int K, int out_dtype, void *out, void *stream);
 /* quantized (or f32/f16/bf16) embedding rows -> f32; role of QuantMethod::embedding_forward (lib.rs:1561, gguf/mod.rs:436) */
 int mrs_embedding(const void *table, int type, const int32_t *ids, float *out, int K, int tokens, void *stream);
 /* round 6, greedy batch-1 step: the arg-max of lm_head folded into its epilogue (mrs_dec_proj_argmax: one u64 packed (value, index) maximum, zero before the launch) and

@@ -141,6 +141,31 @@ def serialize_hqq_layer(prefix: str, w_q, scales, zeros, w_shape, bits: int, gro
     return out
 
 
+def serialize_mxfp4_layer(prefix: str, blocks, scales, bias=None) -> dict:
+    """`MXFP4Layer::serialize_uqff` (mistralrs-quant/src/mxfp4/mod.rs:901-918): name -> tensor, in the reference's order.  blocks u8 [N, K/2] or [E, N, K/2],
+    scales u8 [N, K/32] or [E, N, K/32] (shapes are stored as they are), bias optional in its own dtype (numpy, or a CPU torch tensor for bf16)."""
+    out = {
+        f"{prefix}.{WEIGHT_FORMAT_SUFFIX}": np.array(SERDE_MXFP4, dtype=np.uint8),
+        f"{prefix}.weight": blocks,
+        f"{prefix}.weight.scales": scales,
+    }
+    if bias is not None:
+        out[f"{prefix}.bias"] = bias
+    return out
+
+
+MXFP4_BLOCK_SIZE = 32  # mxfp4/mod.rs:20
+
+
+@dataclass
+class Mxfp4LayerData:
+    """What `MXFP4Layer::from_uqff` reads back (mxfp4/mod.rs:296-323): CPU torch tensors, the shard already applied."""
+    blocks: "torch.Tensor"   # u8 [.., N, K/2]
+    scales: "torch.Tensor"   # u8 [.., N, K/32]
+    bias: "torch.Tensor | None"
+    bias_mode: str           # 'full' | 'skip' | 'narrow'
+
+
 @dataclass
 class HqqLayerData:
     """What `HqqLayer::from_uqff` reads back (hqq/mod.rs:797-826)."""
@@ -292,6 +317,37 @@ class UqffReader:
                             self.load_u8_scalar(f"{prefix}.weight.round_zeros") != 0, self.load_u8_scalar(f"{prefix}.weight.channel_wise") != 0,
                             self._get_torch(key) if key in self._keys else None)
 
+    def load_mxfp4_layer(self, prefix: str, shard: Shard | None = None) -> Mxfp4LayerData:
+        """`MXFP4Layer::from_uqff` (mxfp4/mod.rs:296-323): the logical dims are the blocks' dims with the last one doubled; a shard of that last dim must start
+        and end on a block of 32 and takes `start/2, len/2` of the blocks and `start/32, len/32` of the scales; a shard of another dim applies to both tensors
+        and narrows the bias."""
+        if self.serde_type(prefix) != SERDE_MXFP4:
+            raise ValueError(f"`{prefix}` is not an MXFP4 layer (format {self.serde_type(prefix)})")
+        blocks, scales = self._get_torch(f"{prefix}.weight"), self._get_torch(f"{prefix}.weight.scales")
+        dims = list(blocks.shape)
+        dims[-1] *= 2
+        rng = shard_range(shard, dims)
+        if rng is not None:
+            dim, start, n = rng
+            if dim == len(dims) - 1:
+                if start % MXFP4_BLOCK_SIZE or n % MXFP4_BLOCK_SIZE:
+                    raise ValueError(f"Sharding the MXFP4 packed dim requires alignment of {MXFP4_BLOCK_SIZE}: start {start}, len {n}.")
+                blocks = blocks.narrow(dim, start // 2, n // 2)
+                scales = scales.narrow(dim, start // MXFP4_BLOCK_SIZE, n // MXFP4_BLOCK_SIZE)
+            else:
+                blocks, scales = blocks.narrow(dim, start, n), scales.narrow(dim, start, n)
+        bias, mode = None, "full"
+        if f"{prefix}.bias" in self._keys:
+            mode = bias_shard(rng, len(dims))
+            if mode == "skip":
+                bias = None
+            else:
+                bias = self._get_torch(f"{prefix}.bias")
+                if mode != "full":
+                    _, dim, start, n = mode
+                    bias, mode = bias.narrow(dim, start, n).contiguous(), "narrow"
+        return Mxfp4LayerData(blocks.contiguous(), scales.contiguous(), bias, mode)
+
     def _get_torch(self, key: str):
         """A tensor in its stored dtype (bf16 has no numpy dtype): second handle on the same file, opened on first use."""
         if key not in self._keys:
@@ -302,7 +358,7 @@ class UqffReader:
         return self._ft.get_tensor(key)
 
     def isq_type(self, prefix: str) -> str:
-        """`isq_type_from_uqff` of the layer's serde type: the GGML dtype name for GGUF layers, HQQ8 / HQQ4 for HQQ layers (hqq/mod.rs:1327-1336)."""
+        """`isq_type_from_uqff` of the layer's serde type: the GGML dtype name for GGUF layers, HQQ8 / HQQ4 for HQQ layers (hqq/mod.rs:1327-1336), MXFP4."""
         t = self.serde_type(prefix)
         if t == SERDE_GGUF:
             return GgmlDType.from_id(self.load_u32_scalar(f"{prefix}.weight.dtype")).name
@@ -311,4 +367,6 @@ class UqffReader:
             if bits in (8, 4):
                 return f"HQQ{bits}"
             raise ValueError("Cannot convert HQQ bit width to an ISQ type.")
+        if t == SERDE_MXFP4:  # isq_type_from_uqff (mxfp4/mod.rs:927-929)
+            return "MXFP4"
         raise ValueError(f"serde type {t} has no reader here")
