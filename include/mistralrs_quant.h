@@ -224,6 +224,42 @@ int mxfp4_get_max_smem_optin(void);
  * 3 per-slot MoE GEMV, 4 grouped MoE tile, 5 f16 dense in GEMV chunks of 8 rows; see csrc/mxfp4.hip */
 int mxfp4_last_route(void);
 
+/* ---- Blockwise FP8 (HF `quant_method: fp8, fmt: e4m3, weight_block_size: [bsy, bsx]`): weight [N][K] bytes, OCP E4M3FN (bias 7, no infinities, 0x7f / 0xff NaN,
+ *      max 448); scale f32 [ceil(N / bsy)][scale_row_stride], element (n, k) uses scale[(n / bsy) * stride + k / bsx]; block sizes are any positive integers and
+ *      N, K, height, width need not be multiples of them.  Experts: weights [E][N][K], the scale of expert e starts at e * ceil(N / bsy) * scale_row_stride.
+ *      Dequantize: out[pos] = T(f32(w[pos]) * scale), pos = y * weight_row_stride + x: one f32 product, one conversion (a NaN byte gives NaN).
+ *      Quantize: scale = max(absmax / 448, 1e-12) (correctly rounded f32 division, absmax over the block's in-range elements), q = e4m3_satfinite_rne(f16_rne(
+ *      clamp(f32(v) / scale, +-448))) -- the f32 -> f16 -> e4m3 double rounding is the reference's; inputs are finite.
+ *      Matmul / MoE: out = input . W^T, no bias (the layer adds it in T afterwards).  Every product exact in f32; the products of one scale block are summed
+ *      in f32, that partial sum enters the running f32 sum as fma(scale, partial, total); one rounding to the output type.  indices [num_tokens][topk] u32,
+ *      output [num_tokens][topk][N]; input [num_tokens][K] or, with input_has_topk_dim, [num_tokens][topk][K]; an expert id >= num_experts reads nothing and
+ *      leaves its output row untouched.  Activation pointers need only their element's alignment.  Fast routes need K % 16 == 0, block_size_x % 16 == 0 and
+ *      a 16-byte aligned weight base; anything else takes a correct, untuned kernel (csrc/blockwise_fp8.hip).
+ *      The sm90 entry points of ffi.rs (mistralrs_cutlass_fp8_*, mistralrs_deepgemm_*, mistralrs_fp8_quantize_activation_*) are gated behind cfgs a HIP build
+ *      leaves unset and are not part of this library.
+ *      replaces kernels/blockwise_fp8/blockwise_fp8.cu, blockwise_fp8_gemm.cu ; Rust: src/blockwise_fp8/ffi.rs:127-271 ; callers blockwise_fp8/ops.rs
+ *      (fp8_blockwise_dequantize, fp8_blockwise_quantize, fp8_blockwise_matmul, fp8_indexed_moe_gemm) <- BlockwiseFP8Linear (blockwise_fp8/mod.rs:180-317) */
+#define MRS_DECL_FP8BW(tag)                                                                                                                                  \
+  void launch_dequant_fp8_blockwise_kernel_##tag(const uint8_t *d_weight, const float *d_scale, void *d_output, int weight_height, int weight_width,          \
+                                                 int weight_row_stride, int scale_stride, int weight_block_size_y, int weight_block_size_x, void *stream);   \
+  void launch_quant_fp8_blockwise_kernel_##tag(const void *d_input, uint8_t *d_weight, float *d_scale, int weight_height, int weight_width,                   \
+                                               int weight_row_stride, int scale_stride, int weight_block_size_y, int weight_block_size_x, void *stream);
+MRS_DECL_FP8BW(f32) MRS_DECL_FP8BW(f16) MRS_DECL_FP8BW(bf16)
+#undef MRS_DECL_FP8BW
+void launch_fp8_matmul_f16(const void *input, const uint8_t *weight, const float *weight_scale, void *output, int M, int N, int K, int scale_row_stride,
+                           int block_size_y, int block_size_x, void *stream);
+void launch_fp8_matmul_bf16(const void *input, const uint8_t *weight, const float *weight_scale, void *output, int M, int N, int K, int scale_row_stride,
+                            int block_size_y, int block_size_x, void *stream);
+void launch_fp8_indexed_moe_gemm_f16(const void *input, const uint8_t *weights, const float *weight_scales, const uint32_t *indices, void *output, int num_tokens,
+                                     int topk, int num_experts, int N, int K, int scale_row_stride, int block_size_y, int block_size_x, bool input_has_topk_dim,
+                                     void *stream);
+void launch_fp8_indexed_moe_gemm_bf16(const void *input, const uint8_t *weights, const float *weight_scales, const uint32_t *indices, void *output, int num_tokens,
+                                      int topk, int num_experts, int N, int K, int scale_row_stride, int block_size_y, int block_size_x, bool input_has_topk_dim,
+                                      void *stream);
+/* MI355X-native addition (not in the reference ABI): the route of the last blockwise-FP8 matmul / MoE launch of this process -- 1 streaming GEMV (M <= 8),
+ * 2 16-bit MFMA tile, 3 per-slot MoE GEMV, 4 grouped MoE tile, 5 general (unaligned K / block size / base); see csrc/blockwise_fp8.hip */
+int fp8_blockwise_last_route(void);
+
 /* MI355X-native addition (not in the reference ABI): tile policy of the int8-MFMA MMQ kernels, see csrc/mmq.hip */
 void mrs_mmq_set_small_tiles_below(int n);
 
