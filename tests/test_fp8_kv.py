@@ -149,3 +149,141 @@ def test_update_kv_scales_and_errors(dev):
     with pytest.raises(ValueError, match="block_size 16 or 32"):
         paged_attn.paged_attention(torch.zeros(1, 1, 128, device=dev), kc, vc, torch.zeros(1, 2, dtype=torch.int32, device=dev),
                                    torch.ones(1, dtype=torch.int32, device=dev), 8, 1.0, k_scale=one, v_scale=one)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dt", ["f32", "f16", "bf16"])
+@pytest.mark.parametrize("bs", [16, 32])
+def test_gather_fp8_every_position_with_empty_sequence(oracle, dev, dt, bs):
+    """The fp8 gather at EVERY position of three sequences, the middle one empty: value = T(float(fp8) * scale), bit-exact."""
+    import torch
+    from mistralrs_amd import paged_attn
+    rng = np.random.default_rng(bs * 7 + len(dt))
+    kvh, hd, nb = 2, 64, 8
+    kc, vc = _fp8_cache(rng, nb, kvh, hd, bs)
+    ks, vs = np.float32(0.037), np.float32(0.11)
+    lens = [2 * bs + 3, 0, bs + 1]
+    bt = np.full((3, 4), nb + 1000, dtype=np.int32)  # unused entries point outside the cache: never followed
+    perm = rng.permutation(nb)
+    bt[0, :3], bt[2, :2] = perm[:3], perm[3:5]
+    cu = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+    k_out, v_out = paged_attn.gather_kv_cache(torch.from_numpy(kc).to(dev), torch.from_numpy(vc).to(dev), torch.from_numpy(bt).to(dev),
+                                              torch.from_numpy(cu).to(dev), torch_dtype(dt), torch.tensor([ks], device=dev), torch.tensor([vs], device=dev))
+    kd = round_through(oracle.fp8_e4m3_decode(kc) * ks, dt)
+    vd = round_through(oracle.fp8_e4m3_decode(vc) * vs, dt)
+    parts = [oracle.kv_cache_gather(kd, vd, bt[s], n) for s, n in enumerate(lens) if n]
+    assert tuple(k_out.shape) == (sum(lens), kvh, hd)
+    np.testing.assert_array_equal(k_out.float().cpu().numpy(), np.concatenate([p[0] for p in parts]))
+    np.testing.assert_array_equal(v_out.float().cpu().numpy(), np.concatenate([p[1] for p in parts]))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("bs", [16, 32])
+@pytest.mark.parametrize("force", ["v1", "v2"])
+@pytest.mark.parametrize("opt", ["sinks", "softcap_alibi"])
+def test_paged_attention_fp8_cache_options(oracle, dev, bs, force, opt):
+    """Sinks, and softcap + ALiBi, over the fp8 cache with bf16 queries; bound of test_paged_attention_fp8_cache (pabs evaluated with the same options).
+    16 heads / 4 kv heads, 9 sequences: kv_heads * seqs = 36 > 32 -> G = 4, so the per-head slopes and sinks are read at g = 0..3; the slope of head 1
+    is exactly 0."""
+    import torch
+    from mistralrs_amd import paged_attn
+    dt, heads, kvh, hd = "bf16", 16, 4, 128
+    rng = np.random.default_rng(bs + len(opt))
+    ctxs = [1, bs - 1, bs + 1, 100, 200, 513, 600, 17, 64]
+    seqs = len(ctxs)
+    max_blocks = (max(ctxs) + bs - 1) // bs + 1
+    nb = seqs * max_blocks + 2
+    kc, vc = _fp8_cache(rng, nb, kvh, hd, bs)
+    kc = (kc & 0xBF) | 0x00  # keep |k| < 2 (exponent field < 8) so the logits stay in a sane range
+    kc[(kc & 0x7F) == 0x7F] = 0x30
+    ks, vs = np.float32(0.5), np.float32(0.02)
+    bt = rng.permutation(nb)[: seqs * max_blocks].reshape(seqs, max_blocks).astype(np.int32)
+    q = round_through((rng.standard_normal((seqs, heads, hd)) * 1.5).astype(np.float32), dt)
+    softcap, al, sk = 1.0, None, None
+    if opt == "sinks":
+        sk = rng.standard_normal(heads).astype(np.float32)
+    else:
+        softcap = 30.0
+        al = rng.uniform(0.01, 0.2, heads).astype(np.float32)  # the range of tests/test_paged_attn.py
+        al[1] = 0.0
+    td = torch_dtype(dt)
+    got = paged_attn.paged_attention(torch.from_numpy(q).to(dev).to(td), torch.from_numpy(kc).to(dev), torch.from_numpy(vc).to(dev),
+                                     torch.from_numpy(bt).to(dev), torch.from_numpy(np.array(ctxs, dtype=np.int32)).to(dev), max(ctxs),
+                                     1.0 / np.sqrt(hd), softcapping=softcap, alibi_slopes=torch.from_numpy(al).to(dev) if al is not None else None,
+                                     sinks=torch.from_numpy(sk).to(dev) if sk is not None else None, force=force,
+                                     k_scale=torch.tensor([ks], device=dev), v_scale=torch.tensor([vs], device=dev))
+    kd = round_through(oracle.fp8_e4m3_decode(kc) * ks, dt)
+    vd = round_through(oracle.fp8_e4m3_decode(vc) * vs, dt)
+    kd_std = kd.transpose(0, 1, 2, 4, 3).reshape(nb, kvh, hd, bs)  # [nb, kvh, hd/16, 16, bs] -> [nb, kvh, hd, bs]
+    kd_ref = kd_std.reshape(nb, kvh, hd // 8, 8, bs).transpose(0, 1, 2, 4, 3).copy()
+    want = oracle.paged_attention_ref(q, kd_ref, vd, bt, ctxs, 1.0 / np.sqrt(hd), softcap, al, sk, round_p=lambda p: round_through(p, dt))
+    got = got.float().cpu().numpy()
+    pabs = oracle.paged_attention_ref(q, kd_ref, np.abs(vd), bt, ctxs, 1.0 / np.sqrt(hd), softcap, al, sk)
+    ulp = 2.0 ** -7
+    tol = (2 * ulp + 2e-5) * pabs + ulp * np.abs(want) + 1e-6
+    assert np.isfinite(got).all() and (np.abs(got - want) <= tol).all(), float((np.abs(got - want) / tol).max())
+
+
+def _scale_after(dev, k, v, ks0, vs0):
+    import torch
+    from mistralrs_amd import paged_attn
+    ks, vs = torch.tensor([ks0], dtype=torch.float32, device=dev), torch.tensor([vs0], dtype=torch.float32, device=dev)
+    paged_attn.update_kv_scales(k, v, ks, vs)
+    return np.float32(ks.item()), np.float32(vs.item())
+
+
+def _absmax_over_240(t):
+    """IEEE f32 division of the finite absolute maximum, as the check of test_update_kv_scales_and_errors."""
+    import torch
+    a = t.float().abs()
+    return np.float32(a[torch.isfinite(a)].max().item()) / np.float32(240.0)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dt", ["f32", "f16", "bf16"])
+def test_update_kv_scales_small_edges(dev, dt):
+    """One element; 513 elements (a second block with one live thread); k and v with different maxima at different places (a k / v swap shows);
+    NaNs scattered among finite values never win; an all-zero input and a scale that is already larger stay unchanged."""
+    import torch
+    td = torch_dtype(dt)
+    tiny = np.float32(1e-6)
+    k1, v1 = torch.tensor([-3.0], device=dev).to(td), torch.tensor([0.25], device=dev).to(td)
+    assert _scale_after(dev, k1, v1, tiny, tiny) == (np.float32(3.0) / np.float32(240.0), np.float32(0.25) / np.float32(240.0))
+    g = torch.Generator(device="cpu").manual_seed(2)
+    k = torch.randn(513, generator=g).to(dev).to(td)
+    v = (torch.randn(513, generator=g) * 0.1).to(dev).to(td)
+    k[512], v[0] = -7.5, 1.75   # k: the lone element of the second block; v: the very first element
+    want = (_absmax_over_240(k), _absmax_over_240(v))
+    assert want == (np.float32(7.5) / np.float32(240.0), np.float32(1.75) / np.float32(240.0))
+    assert _scale_after(dev, k, v, tiny, tiny) == want
+    # a scale already above absmax / 240 stays; the other one still moves
+    assert _scale_after(dev, k, v, 1.0, tiny) == (np.float32(1.0), want[1])
+    assert _scale_after(dev, k, v, tiny, 1.0) == (want[0], np.float32(1.0))
+    # NaNs (either sign, first and last element, next to the maximum) are ignored: the comparisons of the kernel never pick them
+    kn, vn = k.clone(), v.clone()
+    kn[[0, 100, 511]] = float("nan")
+    kn[64] = -float("nan")
+    vn[[1, 300, 512]] = float("nan")
+    assert _scale_after(dev, kn, vn, tiny, tiny) == (_absmax_over_240(kn), _absmax_over_240(vn)) == want
+    z = torch.zeros(513, device=dev).to(td)
+    assert _scale_after(dev, z, z, tiny, 0.5) == (tiny, np.float32(0.5))
+    assert _scale_after(dev, z, v, tiny, tiny) == (tiny, want[1])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dt", ["f32", "f16", "bf16"])
+def test_update_kv_scales_block_cap(dev, dt):
+    """512 * 1024 + 37 elements: 1025 blocks are needed, the launch is capped at 1024, so the last 37 elements are reached only by the second trip of the
+    grid-stride loop.  The maximum sits in the last element (k) and in element 0 (v), then the other way round."""
+    import torch
+    td = torch_dtype(dt)
+    n = 512 * 1024 + 37
+    g = torch.Generator(device="cpu").manual_seed(3)
+    base = torch.randn(n, generator=g).clamp_(-4, 4).to(dev).to(td)
+    a, b = base.clone(), base.clone()
+    a[n - 1], b[0] = 100.0, -50.0
+    tiny = np.float32(1e-6)
+    want = (np.float32(100.0) / np.float32(240.0), np.float32(50.0) / np.float32(240.0))
+    assert (_absmax_over_240(a), _absmax_over_240(b)) == want
+    assert _scale_after(dev, a, b, tiny, tiny) == want
+    assert _scale_after(dev, b, a, tiny, tiny) == want[::-1]

@@ -137,7 +137,10 @@ def test_emulated_moe_quantize_q8_1(oracle, be, sym, dt):
 GPU_SUITE_SLICES = [
     ("tests/test_gemm.py", "130-384-512-Q4_K or 1-128-256-Q6_K or (large_m and 256-128-512-False-Q8_0) or slab_producers"),   # MFMA GEMM, both kernels
     ("tests/test_paged_attn.py", "(prefill_attention and 31-0-8-8) or (prefill_attention and 64-45-16-2) or (decode_attention and 8-4-64) "
-                                 "or (llama_shape and v2 and bf16) or reshape_and_cache_f32_into_bf16"),
+                                 "or (llama_shape and v2 and bf16) or reshape_and_cache_f32_into_bf16 "
+                                 # options at G = 4; gather with empty sequences through a strided table; the fp8 cache's block copy
+                                 "or (options_g4 and all-v1-bf16) or (gather_kv_cache_empty and 1-64-bf16-to-f32) or (copy_blocks_other_dtypes and u8)"),
+    ("tests/test_fp8_kv.py", "update_kv_scales_small_edges and bf16"),
     ("tests/test_glue_ops.py", ""),
 ]
 
