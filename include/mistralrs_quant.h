@@ -260,6 +260,42 @@ void launch_fp8_indexed_moe_gemm_bf16(const void *input, const uint8_t *weights,
  * 2 16-bit MFMA tile, 3 per-slot MoE GEMV, 4 grouped MoE tile, 5 general (unaligned K / block size / base); see csrc/blockwise_fp8.hip */
 int fp8_blockwise_last_route(void);
 
+/* ---- AFQ (affine 2/3/4/6/8-bit, the MLX checkpoint format; `--isq 2|3|4|6|8`): w_q u32 [N][K * bits / 32], element j of a row in bits [j * bits, (j + 1) * bits) of
+ *      the row's little-endian bit stream (3- and 6-bit codes may straddle two words; the byte-wise view of the 3- / 6-bit symbols is the same stream; a row is
+ *      4-byte aligned only); scales / biases T [N][K / group], group 32 / 64 / 128, K % group == 0; weight = q * scale + bias.
+ *      Dequantize / embedding: T(fmaf(q, scale, bias)), one conversion.  Quantize: the reference's CPU rule (afq/ops.rs:1534-1622) for every width: scale =
+ *      (max - min) / (2^bits - 1) (1 when |max - min| < 1e-12), bias = min, q = clamp(roundf((w - bias) / scale)), true f32 divisions, f32 scale and bias.
+ *      qmv / qmm: y [m][n] = x [m][k] . W^T; both names dispatch by m: streaming GEMV (m <= 8), code-operand MFMA tile (bf16 / f16), GEMV chunks (f32).
+ *      f32 accumulation in the grouped form sum_g (s_g sum x q + b_g sum x), one rounding to T.  NO stream argument (null stream), as the reference.
+ *      replaces kernels/afq/afq.cu, afq_gemm.cu ; Rust: src/afq/ffi.rs ; callers afq/ops.rs (afq_quantize_op, afq_dequantize_op, afq_embedding_op, afq_mm_op)
+ *      <- AfqLayer (afq/mod.rs) */
+#define MRS_DECL_AFQ(B, G, T, tag, WQ)                                                                                                                 \
+  void afq_dequantize_##B##bit_gs##G##_##tag(const WQ *w_q, const T *scales, const T *biases, T *output, int rows, int cols);                          \
+  void afq_embedding_##B##bit_gs##G##_##tag(const uint8_t *w_q, const T *scales, const T *biases, const uint32_t *ids, T *output, int num_ids, int hidden); \
+  void afq_qmv_##B##bit_gs##G##_##tag(const T *x, const WQ *w_q, const T *scales, const T *biases, T *y, int m, int n, int k);
+#define MRS_DECL_AFQ_P2(B, G, T, tag)                                                                                                                  \
+  MRS_DECL_AFQ(B, G, T, tag, uint32_t)                                                                                                                 \
+  void afq_quantize_##B##bit_gs##G##_##tag(const T *w, uint32_t *w_q, T *scales, T *biases, int rows, int cols);                                       \
+  void afq_qmm_##B##bit_gs##G##_##tag(const T *x, const uint32_t *w_q, const T *scales, const T *biases, T *y, int m, int n, int k);
+#define MRS_DECL_AFQ_G(G, T, tag)                                                                                                                      \
+  MRS_DECL_AFQ_P2(2, G, T, tag) MRS_DECL_AFQ(3, G, T, tag, uint8_t) MRS_DECL_AFQ_P2(4, G, T, tag) MRS_DECL_AFQ(6, G, T, tag, uint8_t) MRS_DECL_AFQ_P2(8, G, T, tag)
+#define MRS_DECL_AFQ_T(T, tag) MRS_DECL_AFQ_G(32, T, tag) MRS_DECL_AFQ_G(64, T, tag) MRS_DECL_AFQ_G(128, T, tag)
+MRS_DECL_AFQ_T(float, f32)
+MRS_DECL_AFQ_T(uint16_t, f16)  /* IEEE half bits */
+MRS_DECL_AFQ_T(uint16_t, bf16) /* bfloat16 bits */
+#undef MRS_DECL_AFQ_T
+#undef MRS_DECL_AFQ_G
+#undef MRS_DECL_AFQ_P2
+#undef MRS_DECL_AFQ
+/* MI355X-native additions (not in the reference ABI): the stream-taking launchers behind the symbols above and behind mrs_afq_matmul /
+ * mrs_afq_indexed_moe_gemm of include/mrs_hip_ext.h (same arguments, see there), and the route of the last AFQ matmul / MoE launch of this process -- 1 streaming
+ * GEMV (M <= 8), 2 code-operand MFMA tile, 3 per-slot MoE GEMV, 4 grouped MoE tile, 5 f32 dense in GEMV chunks of 8 rows; see csrc/afq.hip */
+int launch_afq_matmul(const void *x, const void *w_q, const void *scales, const void *biases, const void *bias, void *y, int M, int N, int K, int bits, int group,
+                      int dtype, void *stream);
+int launch_afq_indexed_moe_gemm(const void *x, const void *w_q, const void *scales, const void *biases, const void *bias, const uint32_t *indices, void *y,
+                                int num_tokens, int topk, int num_experts, int N, int K, int bits, int group, int dtype, int input_has_topk_dim, void *stream);
+int afq_last_route(void);
+
 /* MI355X-native addition (not in the reference ABI): tile policy of the int8-MFMA MMQ kernels, see csrc/mmq.hip */
 void mrs_mmq_set_small_tiles_below(int n);
 

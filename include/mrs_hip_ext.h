@@ -144,6 +144,23 @@ int mrs_hqq_gemv(int bits, int dtype, const void *wq, const void *scale, const v
  * value table[nibble] * f32_from_bits(scale << 23) is exact and converted once.  out_dtype 0 = f32, 1 = f16, 2 = bf16.  Role: MXFP4Layer::dequantize_w and
  * embedding_forward_raw (mxfp4/mod.rs:87-103,615-707), both CPU loops in the reference.  0 on success, < 0 for arguments outside the kernel. */
 int mrs_mxfp4_dequantize_rows(const void *blocks, const void *scales, const int32_t *ids, int64_t rows, int K, int out_dtype, void *out, void *stream);
+
+/* AFQ (affine 2/3/4/6/8-bit; format and arithmetic in include/mistralrs_quant.h and csrc/afq_core.cuh), stream-taking entry points (ext_afq.hip).  bits in
+ * {2, 3, 4, 6, 8}, group in {32, 64, 128}, K % group == 0, dtype 0 = f32 / 1 = f16 / 2 = bf16 for x, scales, biases, bias and the output alike.  Each returns 0,
+ * or < 0 for arguments outside the kernels.
+ *   mrs_afq_matmul            y [M][N] = x [M][K] . W^T (+ bias [N], may be null), routes 1 / 2 / 5 of csrc/afq.hip by M and dtype.
+ *   mrs_afq_indexed_moe_gemm  w_q [E][N][K * bits / 32], scales / biases [E][N][K / group], bias [E][N] or null, indices [num_tokens][topk] u32, y
+ *                             [num_tokens][topk][N]; x [num_tokens][K] or, with input_has_topk_dim, [num_tokens][topk][K]; an expert id >= num_experts reads
+ *                             nothing and leaves its output row untouched.  Routes 3 / 4.
+ *   mrs_afq_dequantize_rows   out row r [K] = the dequantized row ids[r] (r when ids is null): AfqLayer::dequantize_w and embedding_forward_raw.
+ *   mrs_afq_quantize          w [rows][K] -> w_q, scales, biases by the reference's CPU rule, all five widths. */
+int mrs_afq_matmul(const void *x, const void *w_q, const void *scales, const void *biases, const void *bias, void *y, int M, int N, int K, int bits, int group,
+                   int dtype, void *stream);
+int mrs_afq_indexed_moe_gemm(const void *x, const void *w_q, const void *scales, const void *biases, const void *bias, const uint32_t *indices, void *y,
+                             int num_tokens, int topk, int num_experts, int N, int K, int bits, int group, int dtype, int input_has_topk_dim, void *stream);
+int mrs_afq_dequantize_rows(const void *w_q, const void *scales, const void *biases, const uint32_t *ids, int64_t rows, int K, int bits, int group, int dtype,
+                            void *out, void *stream);
+int mrs_afq_quantize(const void *w, void *w_q, void *scales, void *biases, int64_t rows, int K, int bits, int group, int dtype, void *stream);
 /* quantized (or f32/f16/bf16) embedding rows -> f32; role of QuantMethod::embedding_forward (lib.rs:1561, gguf/mod.rs:436) */
 int mrs_embedding(const void *table, int type, const int32_t *ids, float *out, int K, int tokens, void *stream);
 /* round 6, greedy batch-1 step: the arg-max of lm_head folded into its epilogue (mrs_dec_proj_argmax: one u64 packed (value, index) maximum, zero before the launch) and

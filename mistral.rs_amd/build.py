@@ -54,9 +54,9 @@ def libraries():
     libs["libmistralrspagedattention.so"] = pa
     # optional translation units are picked up as soon as the file exists
     optional = {
-        "libmistralrsquant.so": ["quant_ops.hip", "mmq.hip", "moe.hip", "gemv.hip", "hqq.hip", "mxfp4.hip", "blockwise_fp8.hip"],
+        "libmistralrsquant.so": ["quant_ops.hip", "mmq.hip", "moe.hip", "gemv.hip", "hqq.hip", "mxfp4.hip", "blockwise_fp8.hip", "afq.hip"],
         "libmistralrscuda.so": ["core_ops.hip", "sampling.hip"],
-        "libmrs_hip_ext.so": ["ext_decode.hip", "ext_dec.hip", "ext_dec_mm.hip", "ext_gemm.hip", "ext_gemm_qi.hip", "ext_attn_prefill.hip", "ext_comm.hip", "ext_p2p.hip", "ext_hqq_gemv.hip", "ext_isq.hip", "ext_prefetch.hip", "ext_gemm_lt.hip", "ext_mxfp4.hip",
+        "libmrs_hip_ext.so": ["ext_decode.hip", "ext_dec.hip", "ext_dec_mm.hip", "ext_gemm.hip", "ext_gemm_qi.hip", "ext_attn_prefill.hip", "ext_comm.hip", "ext_p2p.hip", "ext_hqq_gemv.hip", "ext_isq.hip", "ext_prefetch.hip", "ext_gemm_lt.hip", "ext_mxfp4.hip", "ext_afq.hip",
                               "host/runtime.cpp", "host/kv_cache_manager.cpp"],
     }
     # experiment knob (default off): MRS_DECODE_MIN_WAVES=4 caps the decode GEMV kernels at 128 VGPRs (csrc/ext_decode.hip); use with --force
@@ -118,7 +118,12 @@ def build(jobs: int | None = None, force: bool = False, verbose: bool = True) ->
     jobs = jobs or min(16, os.cpu_count() or 4)
     out = {}
     with cf.ThreadPoolExecutor(jobs) as ex:
-        futs = {name: [ex.submit(_compile, *tu, force, hdr_m) for tu in tus] for name, tus in libs.items()}
+        # largest sources first: the long translation units (the ext_* ones, listed last) would otherwise start last and leave a tail on a few cores
+        order = sorted(((name, i) for name, tus in libs.items() for i in range(len(tus))),
+                       key=lambda ni: -os.path.getsize(os.path.join(CSRC, libs[ni[0]][ni[1]][0])))
+        futs = {name: [None] * len(tus) for name, tus in libs.items()}
+        for name, i in order:
+            futs[name][i] = ex.submit(_compile, *libs[name][i], force, hdr_m)
         for name, fl in sorted(futs.items(), key=lambda kv: kv[0] == "libmrs_hip_ext.so"):  # ext links last
             res = [f.result() for f in fl]
             objs = [o for o, _ in res]

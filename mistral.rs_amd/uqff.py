@@ -154,7 +154,39 @@ def serialize_mxfp4_layer(prefix: str, blocks, scales, bias=None) -> dict:
     return out
 
 
+def serialize_afq_layer(prefix: str, w_q, scales, biases, bits: int, group_size: int, bias=None) -> dict:
+    """`AfqLayer::serialize_uqff` (mistralrs-quant/src/afq/mod.rs:536-562): name -> tensor, in the reference's order.  w_q u32 [.., N, K * bits / 32], scales and
+    biases [.., N, K / group] in their own dtype (CPU torch tensors), bits and group size as u8 scalars."""
+    if bits not in (2, 3, 4, 6, 8):
+        raise ValueError(f"Invalid AFQ bits {bits}.")
+    if group_size not in (32, 64, 128):
+        raise ValueError(f"Invalid AFQ group size {group_size}.")
+    out = {
+        f"{prefix}.{WEIGHT_FORMAT_SUFFIX}": np.array(SERDE_AFQ, dtype=np.uint8),
+        f"{prefix}.weight.bits": np.array(bits, dtype=np.uint8),
+        f"{prefix}.weight.group_size": np.array(group_size, dtype=np.uint8),
+        f"{prefix}.weight": w_q,
+        f"{prefix}.weight.scales": scales,
+        f"{prefix}.weight.biases": biases,
+    }
+    if bias is not None:
+        out[f"{prefix}.bias"] = bias
+    return out
+
+
 MXFP4_BLOCK_SIZE = 32  # mxfp4/mod.rs:20
+
+
+@dataclass
+class AfqLayerData:
+    """What `AfqLayer::from_uqff` reads back (afq/mod.rs:393-432): CPU torch tensors, the shard already applied."""
+    w_q: "torch.Tensor"      # u32 [.., N, K * bits / 32]
+    scales: "torch.Tensor"   # [.., N, K / group]
+    biases: "torch.Tensor"
+    bias: "torch.Tensor | None"
+    bits: int
+    group_size: int
+    bias_mode: str           # 'full' | 'skip' | 'narrow'
 
 
 @dataclass
@@ -348,6 +380,43 @@ class UqffReader:
                     bias, mode = bias.narrow(dim, start, n).contiguous(), "narrow"
         return Mxfp4LayerData(blocks.contiguous(), scales.contiguous(), bias, mode)
 
+    def load_afq_layer(self, prefix: str, shard: Shard | None = None) -> AfqLayerData:
+        """`AfqLayer::from_uqff` (afq/mod.rs:393-432): the logical dims are the scales' dims with the last one times the group size; a shard of that last dim must
+        start and end on a group boundary and takes `start * bits / 32, len * bits / 32` words and `start / group, len / group` groups; a shard of another dim
+        applies to all three tensors and narrows the bias."""
+        if self.serde_type(prefix) != SERDE_AFQ:
+            raise ValueError(f"`{prefix}` is not an AFQ layer (format {self.serde_type(prefix)})")
+        bits = self.load_u8_scalar(f"{prefix}.weight.bits")
+        if bits not in (2, 3, 4, 6, 8):
+            raise ValueError(f"Invalid AFQ bits {bits}.")
+        group = self.load_u8_scalar(f"{prefix}.weight.group_size")
+        if group not in (32, 64, 128):
+            raise ValueError(f"Invalid AFQ group size {group}.")
+        w_q, scales, biases = self._get_torch(f"{prefix}.weight"), self._get_torch(f"{prefix}.weight.scales"), self._get_torch(f"{prefix}.weight.biases")
+        dims = list(scales.shape)
+        dims[-1] *= group
+        rng = shard_range(shard, dims)
+        if rng is not None:
+            dim, start, n = rng
+            if dim == len(dims) - 1:
+                if start % group or n % group:
+                    raise ValueError(f"Sharding the AFQ packed dim requires group alignment: start {start}, len {n}, group {group}.")
+                w_q = w_q.narrow(dim, start * bits // 32, n * bits // 32)
+                scales, biases = scales.narrow(dim, start // group, n // group), biases.narrow(dim, start // group, n // group)
+            else:
+                w_q, scales, biases = w_q.narrow(dim, start, n), scales.narrow(dim, start, n), biases.narrow(dim, start, n)
+        bias, mode = None, "full"
+        if f"{prefix}.bias" in self._keys:
+            mode = bias_shard(rng, len(dims))
+            if mode == "skip":
+                bias = None
+            else:
+                bias = self._get_torch(f"{prefix}.bias")
+                if mode != "full":
+                    _, dim, start, n = mode
+                    bias, mode = bias.narrow(min(dim, bias.dim() - 1), start, n).contiguous(), "narrow"
+        return AfqLayerData(w_q.contiguous(), scales.contiguous(), biases.contiguous(), bias, bits, group, mode)
+
     def _get_torch(self, key: str):
         """A tensor in its stored dtype (bf16 has no numpy dtype): second handle on the same file, opened on first use."""
         if key not in self._keys:
@@ -358,7 +427,7 @@ class UqffReader:
         return self._ft.get_tensor(key)
 
     def isq_type(self, prefix: str) -> str:
-        """`isq_type_from_uqff` of the layer's serde type: the GGML dtype name for GGUF layers, HQQ8 / HQQ4 for HQQ layers (hqq/mod.rs:1327-1336), MXFP4."""
+        """`isq_type_from_uqff` of the layer's serde type: the GGML dtype name for GGUF layers, HQQ8 / HQQ4 for HQQ layers (hqq/mod.rs:1327-1336), MXFP4, AFQ2 .. AFQ8."""
         t = self.serde_type(prefix)
         if t == SERDE_GGUF:
             return GgmlDType.from_id(self.load_u32_scalar(f"{prefix}.weight.dtype")).name
@@ -369,4 +438,9 @@ class UqffReader:
             raise ValueError("Cannot convert HQQ bit width to an ISQ type.")
         if t == SERDE_MXFP4:  # isq_type_from_uqff (mxfp4/mod.rs:927-929)
             return "MXFP4"
+        if t == SERDE_AFQ:  # isq_type_from_uqff (afq/mod.rs:571-580)
+            bits = self.load_u8_scalar(f"{prefix}.weight.bits")
+            if bits not in (2, 3, 4, 6, 8):
+                raise ValueError(f"Invalid AFQ bits {bits}.")
+            return f"AFQ{bits}"
         raise ValueError(f"serde type {t} has no reader here")
