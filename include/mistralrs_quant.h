@@ -296,6 +296,32 @@ int launch_afq_indexed_moe_gemm(const void *x, const void *w_q, const void *scal
                                 int num_tokens, int topk, int num_experts, int N, int K, int bits, int group, int dtype, int input_has_topk_dim, void *stream);
 int afq_last_route(void);
 
+/* ---- GPTQ / AWQ (`quantization_config.quant_method` "gptq" / "awq"): qweight u32 [K * bits / 32][N], column n holds its K codes as one little-endian bit stream
+ *      down the rows (3-bit codes 10 and 21 of every 32 straddle two words); qzeros u32 [G][N * bits / 32], the same stream along N; scales f16 [G][N]; g_idx i32
+ *      [K], any map from row to group (act-order), values in [0, G) (not checked here); bits 2 / 3 / 4 / 8; K % 32 == 0, N % 32 == 0.
+ *      W[k][n] = f16_rne((q - (z + 1)) * s), z + 1 not wrapped: one f16 multiply of an exact integer, the value of the reference's reconstruct_gptq.
+ *      reconstruct_gptq: out f16 [size_k][size_n] row-major.  gemm_half_q_half_alt: out [m][n] = f16_rne(sum_k a[m][k] W[k][n]) with f32 accumulation, every
+ *      element written once by a plain store (the reference accumulates in f16 with atomicAdd into a zeroed output); any m (streaming GEMV for m <= 8, f16 MFMA
+ *      tile above) and bits 2 / 3 / 4 / 8 (the reference: 4 / 8).  NO stream argument (null stream), as the reference.
+ *      reconstruct_exllama and gemm_half_q_half_cuda_part are NOT declared: they take exllama-shuffled weights, and the reference's gptq_linear always builds its
+ *      layers with use_exllama = false; the Marlin routes are an NVIDIA layout.
+ *      replaces kernels/gptq/q_gemm.cu ; Rust: src/gptq/ffi.rs ; caller GptqLayer::gptq_gemm (gptq/gptq_cuda.rs:176-283) */
+void reconstruct_gptq(const uint32_t *b_q_weight, const uint32_t *b_qzeros, const uint16_t *b_scales, const int *b_q_perm, uint16_t *out, int size_k, int size_n,
+                      int groups, int bit);
+void gemm_half_q_half_alt(const uint16_t *a, const uint32_t *b_q_weight, const uint32_t *b_qzeros, const uint16_t *b_scales, const int *b_g_idx, uint16_t *out, int m,
+                          int n, int k, int bit);
+/* MI355X-native additions (not in the reference ABI): the stream-taking launchers behind the symbols above and behind mrs_gptq_matmul / mrs_gptq_reconstruct /
+ * mrs_awq_repack of include/mrs_hip_ext.h (same arguments, see there); zero_offset is 1 for GPTQ tensors and 0 for AWQ tensors after launch_awq_repack.  Each
+ * returns 0, or -1 for arguments outside the kernels (-2 / -3: launch too large / launch error).  gptq_last_route: the route of the last GPTQ matmul of this
+ * process -- 1 streaming GEMV (M <= 8), 2 f16 MFMA tile; see csrc/gptq.hip */
+int launch_gptq_matmul(const void *x, const void *qweight, const void *qzeros, const void *scales, const void *g_idx, const void *bias, void *y, int M, int N, int K,
+                       int groups, int bits, int zero_offset, void *stream);
+int launch_gptq_reconstruct(const void *qweight, const void *qzeros, const void *scales, const void *g_idx, void *out, int K, int N, int groups, int bits,
+                            int zero_offset, void *stream);
+int launch_awq_repack(const void *qweight, const void *qzeros, void *qweight_out, void *qzeros_out, void *g_idx_out, int K, int N, int groups, int group_size,
+                      int bits, void *stream);
+int gptq_last_route(void);
+
 /* MI355X-native addition (not in the reference ABI): tile policy of the int8-MFMA MMQ kernels, see csrc/mmq.hip */
 void mrs_mmq_set_small_tiles_below(int n);
 

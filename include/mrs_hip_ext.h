@@ -161,6 +161,23 @@ int mrs_afq_indexed_moe_gemm(const void *x, const void *w_q, const void *scales,
 int mrs_afq_dequantize_rows(const void *w_q, const void *scales, const void *biases, const uint32_t *ids, int64_t rows, int K, int bits, int group, int dtype,
                             void *out, void *stream);
 int mrs_afq_quantize(const void *w, void *w_q, void *scales, void *biases, int64_t rows, int K, int bits, int group, int dtype, void *stream);
+
+/* GPTQ / AWQ (format and arithmetic in include/mistralrs_quant.h and csrc/gptq.hip), stream-taking entry points (ext_gptq.hip).  GPTQ layout: qweight u32
+ * [K * bits / 32][N], qzeros u32 [groups][N * bits / 32], scales f16 [groups][N], g_idx i32 [K] with values in [0, groups) (the caller checks them); bits in
+ * {2, 3, 4, 8}, K % 32 == 0, N % 32 == 0; x, bias and the output are f16.  zero_offset: 1 for GPTQ checkpoints, 0 for AWQ ones after mrs_awq_repack.  Each
+ * returns 0, or < 0 for arguments outside the kernels.
+ *   mrs_gptq_matmul       y [M][N] = f16_rne(sum_k x[m][k] W[k][n] + bias[n]) (bias [N] may be null), f32 accumulation, one rounding; routes 1 / 2 of
+ *                         csrc/gptq.hip by M; every element written once, no dependence on what y held.
+ *   mrs_gptq_reconstruct  out f16 [K][N] row-major, W[k][n] = f16_rne((q - (z + zero_offset)) * s): GptqLayer::dequantize_w is its transpose.
+ *   mrs_awq_repack        AWQ qweight u32 [K][N * bits / 32] and qzeros u32 [groups][N * bits / 32] (packed along N, interleaved {0,4,1,5,2,6,3,7} at 4 bits,
+ *                         {0,2,1,3} at 8) -> qweight_out [K * bits / 32][N], qzeros_out [groups][N * bits / 32] in GPTQ layout and g_idx_out[k] = k / group_size;
+ *                         bits 4 / 8, groups == K / group_size; bit exact, run once at load time. */
+int mrs_gptq_matmul(const void *x, const void *qweight, const void *qzeros, const void *scales, const void *g_idx, const void *bias, void *y, int M, int N, int K,
+                    int groups, int bits, int zero_offset, void *stream);
+int mrs_gptq_reconstruct(const void *qweight, const void *qzeros, const void *scales, const void *g_idx, void *out, int K, int N, int groups, int bits,
+                         int zero_offset, void *stream);
+int mrs_awq_repack(const void *qweight, const void *qzeros, void *qweight_out, void *qzeros_out, void *g_idx_out, int K, int N, int groups, int group_size, int bits,
+                   void *stream);
 /* quantized (or f32/f16/bf16) embedding rows -> f32; role of QuantMethod::embedding_forward (lib.rs:1561, gguf/mod.rs:436) */
 int mrs_embedding(const void *table, int type, const int32_t *ids, float *out, int K, int tokens, void *stream);
 /* round 6, greedy batch-1 step: the arg-max of lm_head folded into its epilogue (mrs_dec_proj_argmax: one u64 packed (value, index) maximum, zero before the launch) and
