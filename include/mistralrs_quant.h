@@ -322,6 +322,47 @@ int launch_awq_repack(const void *qweight, const void *qzeros, void *qweight_out
                       int bits, void *stream);
 int gptq_last_route(void);
 
+/* ---- per-tensor FP8 (OCP E4M3FN bytes + ONE f32 scale per tensor): FP8Linear (`--isq fp8`, UQFF serde type 3) and PerTensorFP8Linear (HF `quant_method: fp8`
+ *      with `weight_block_size: null`).  fp8 -> T is exact (0x7f / 0xff give NaN); T -> fp8 is e4m3_satfinite_rne(f16_rne(clamp(f32(v), +-448))).
+ *      The six scalar conversions have the signatures of src/scalar_fp8/ffi.rs; the stream slot is a hipStream_t (void * here).
+ *      replaces kernels/scalar_fp8/scalar_fp8.cu ; Rust: src/scalar_fp8/ffi.rs ; callers scalar_fp8/ops.rs, fp8/quantize.rs, pertensor_fp8/ops.rs */
+void launch_fp8_to_f32_kernel(const uint8_t *d_input, float *d_output, size_t num_elements, void *stream);
+void launch_fp8_to_f16_kernel(const uint8_t *d_input, void *d_output, size_t num_elements, void *stream);
+void launch_fp8_to_bf16_kernel(const uint8_t *d_input, void *d_output, size_t num_elements, void *stream);
+void launch_f32_to_fp8_kernel(const float *d_input, uint8_t *d_output, size_t num_elements, void *stream);
+void launch_f16_to_fp8_kernel(const void *d_input, uint8_t *d_output, size_t num_elements, void *stream);
+void launch_bf16_to_fp8_kernel(const void *d_input, uint8_t *d_output, size_t num_elements, void *stream);
+/* MI355X-native additions (not in the reference ABI; its W8A8 forward is a cuBLASLt call), csrc/fp8_pertensor.hip.  <tag> = f32 / f16 / bf16, the source or
+ * destination type.  Each returns 0, or -1 for arguments outside the kernels (-2 / -3: launch too large / launch error).
+ *   `state` is f32 [fp8_pertensor_state_floats()] on the device: state[0] = amax = max |f32(x)|, state[1] = s = min(448 / amax, 448) (448 for amax == 0),
+ *   state[2] = dq = 1 / s, the rest the per-workgroup maxima of the two-stage reduction.  Nothing synchronises with the host; the same bits on every run.
+ *   absmax            fills state from in [n].
+ *   quantize_dynamic  absmax, then q[i] = fp8(f32(in[i]) * s): one f32 product.
+ *   quantize_static   q[i] = fp8(f32(in[i]) / *scale), the correctly rounded division; a null scale means 1.
+ *   dequantize        out [rows][K] = T(f32(w[row]) * *scale), one f32 product and one RNE conversion; `ids` (i32 [rows], may be null) picks the source rows and
+ *                     is trusted to lie inside w; a null scale means 1.
+ *   matmul            out [M][N] = RNE_T(fmaf(S, *dq_x * *dq_w, f32(bias[n]))), S = sum_k f32(xq[m][k]) f32(wq[n][k]), T = the tag (f16 / bf16), bias [N] of T or null.
+ *                     Every product is exact in f32.  Route 3 adds them in f32.  Routes 1 and 2 add them on the FP8 matrix core, which is NOT an f32 sum: inside one
+ *                     MFMA (32 products on route 1, 16 on route 2) each product is cut toward zero onto the grid 2^(e - 13), e the exponent of that instruction's
+ *                     largest product; the instructions' results are added in f32.  Exact when the products lie on that grid; a row's bits may differ between an
+ *                     M = 16 and an M = 17 call.  fp8_pertensor_last_route: 1 skinny FP8 MFMA GEMV (K % 16 == 0, 16-byte aligned xq / wq, M <= 16), 2 FP8 MFMA
+ *                     tile (the same, M > 16), 3 general. */
+#define MRS_FP8_PERTENSOR_DECL(tag)                                                                                                  \
+  int launch_fp8_pertensor_absmax_##tag(const void *in, size_t n, float *state, void *stream);                                       \
+  int launch_fp8_pertensor_quantize_dynamic_##tag(const void *in, uint8_t *q, size_t n, float *state, void *stream);                 \
+  int launch_fp8_pertensor_quantize_static_##tag(const void *in, uint8_t *q, size_t n, const float *scale, void *stream);            \
+  int launch_fp8_pertensor_dequantize_##tag(const uint8_t *w, const float *scale, const int32_t *ids, void *out, long long rows, int K, void *stream);
+MRS_FP8_PERTENSOR_DECL(f32)
+MRS_FP8_PERTENSOR_DECL(f16)
+MRS_FP8_PERTENSOR_DECL(bf16)
+#undef MRS_FP8_PERTENSOR_DECL
+int launch_fp8_pertensor_matmul_f16(const uint8_t *xq, const uint8_t *wq, const float *dq_x, const float *dq_w, const void *bias, void *out, int M, int N, int K,
+                                    void *stream);
+int launch_fp8_pertensor_matmul_bf16(const uint8_t *xq, const uint8_t *wq, const float *dq_x, const float *dq_w, const void *bias, void *out, int M, int N, int K,
+                                     void *stream);
+int fp8_pertensor_state_floats(void);
+int fp8_pertensor_last_route(void);
+
 /* MI355X-native addition (not in the reference ABI): tile policy of the int8-MFMA MMQ kernels, see csrc/mmq.hip */
 void mrs_mmq_set_small_tiles_below(int n);
 

@@ -178,6 +178,14 @@ int mrs_gptq_reconstruct(const void *qweight, const void *qzeros, const void *sc
                          int zero_offset, void *stream);
 int mrs_awq_repack(const void *qweight, const void *qzeros, void *qweight_out, void *qzeros_out, void *g_idx_out, int K, int N, int groups, int group_size, int bits,
                    void *stream);
+
+/* Per-tensor FP8 (format and arithmetic in include/mistralrs_quant.h and csrc/fp8_pertensor.hip), stream-taking entry points (ext_fp8.hip) that pick the typed
+ * launcher by `dtype`: 0 f32, 1 f16, 2 bf16 (the source of a quantizer, the destination of dequantize, the output and bias type of the matmul: 1 or 2 only).
+ * Arguments as launch_fp8_pertensor_{quantize_dynamic,quantize_static,dequantize,matmul}_<tag>.  Each returns 0, or < 0 for arguments outside the kernels. */
+int mrs_fp8_quantize_dynamic(const void *in, void *q, size_t n, float *state, int dtype, void *stream);
+int mrs_fp8_quantize_static(const void *in, void *q, size_t n, const float *scale, int dtype, void *stream);
+int mrs_fp8_dequantize(const void *w, const float *scale, const int32_t *ids, void *out, long long rows, int K, int dtype, void *stream);
+int mrs_fp8_matmul(const void *xq, const void *wq, const float *dq_x, const float *dq_w, const void *bias, void *out, int M, int N, int K, int dtype, void *stream);
 /* quantized (or f32/f16/bf16) embedding rows -> f32; role of QuantMethod::embedding_forward (lib.rs:1561, gguf/mod.rs:436) */
 int mrs_embedding(const void *table, int type, const int32_t *ids, float *out, int K, int tokens, void *stream);
 /* round 6, greedy batch-1 step: the arg-max of lm_head folded into its epilogue (mrs_dec_proj_argmax: one u64 packed (value, index) maximum, zero before the launch) and

@@ -174,7 +174,36 @@ def serialize_afq_layer(prefix: str, w_q, scales, biases, bits: int, group_size:
     return out
 
 
+def serialize_fp8_layer(prefix: str, weight, dequant_w_scale, dequant_x_scale, quant_scale, bias=None, dtype_code: int = 9) -> dict:
+    """`FP8Linear::serialize_uqff` (mistralrs-quant/src/fp8/mod.rs:312-341): name -> tensor, in the reference's order.  weight [N, K] float8_e4m3fn (or its u8
+    bytes), the three scales f32 scalars, `weight.dtype` the UQFF code of the quantized type (9 = F8E4M3, utils/uqff.rs:3-21); CPU torch tensors."""
+    scalar = lambda t: t.reshape(())  # rank 0, as candle's scalar tensors are stored
+    out = {
+        f"{prefix}.{WEIGHT_FORMAT_SUFFIX}": np.array(SERDE_FP8, dtype=np.uint8),
+        f"{prefix}.weight": weight,
+        f"{prefix}.weight.dequant_w_scale": scalar(dequant_w_scale),
+        f"{prefix}.weight.dequant_x_scale": scalar(dequant_x_scale),
+        f"{prefix}.weight.quant_scale": scalar(quant_scale),
+        f"{prefix}.weight.dtype": np.array(dtype_code, dtype=np.uint32),
+    }
+    if bias is not None:
+        out[f"{prefix}.bias"] = bias
+    return out
+
+
 MXFP4_BLOCK_SIZE = 32  # mxfp4/mod.rs:20
+
+
+@dataclass
+class Fp8LayerData:
+    """What `FP8Linear::from_uqff` reads back (fp8/mod.rs:74-93): CPU torch tensors, the shard applied to the weight and the bias."""
+    weight: "torch.Tensor"           # float8_e4m3fn (or u8) [N, K]
+    dequant_w_scale: "torch.Tensor"  # f32 scalars
+    dequant_x_scale: "torch.Tensor"
+    quant_scale: "torch.Tensor"
+    dtype_code: int
+    bias: "torch.Tensor | None"
+    bias_mode: str                   # 'full' | 'skip' | 'narrow'
 
 
 @dataclass
@@ -417,6 +446,29 @@ class UqffReader:
                     bias, mode = bias.narrow(min(dim, bias.dim() - 1), start, n).contiguous(), "narrow"
         return AfqLayerData(w_q.contiguous(), scales.contiguous(), biases.contiguous(), bias, bits, group, mode)
 
+    def load_fp8_layer(self, prefix: str, shard: Shard | None = None) -> Fp8LayerData:
+        """`FP8Linear::from_uqff` (fp8/mod.rs:74-93): `shard_range` over the weight's own dims narrows the weight, and the bias when the output dim is sharded;
+        the three scales are per tensor and load whole."""
+        if self.serde_type(prefix) != SERDE_FP8:
+            raise ValueError(f"`{prefix}` is not an FP8 layer (format {self.serde_type(prefix)})")
+        weight = self._get_torch(f"{prefix}.weight")
+        dims = list(weight.shape)
+        rng = shard_range(shard, dims)
+        if rng is not None:
+            weight = weight.narrow(*rng)
+        bias, mode = None, "full"
+        if f"{prefix}.bias" in self._keys:
+            mode = bias_shard(rng, len(dims))
+            if mode == "skip":
+                bias = None
+            else:
+                bias = self._get_torch(f"{prefix}.bias")
+                if mode != "full":
+                    _, dim, start, n = mode
+                    bias, mode = bias.narrow(min(dim, bias.dim() - 1), start, n).contiguous(), "narrow"
+        return Fp8LayerData(weight.contiguous(), self._get_torch(f"{prefix}.weight.dequant_w_scale"), self._get_torch(f"{prefix}.weight.dequant_x_scale"),
+                            self._get_torch(f"{prefix}.weight.quant_scale"), self.load_u32_scalar(f"{prefix}.weight.dtype"), bias, mode)
+
     def _get_torch(self, key: str):
         """A tensor in its stored dtype (bf16 has no numpy dtype): second handle on the same file, opened on first use."""
         if key not in self._keys:
@@ -427,7 +479,7 @@ class UqffReader:
         return self._ft.get_tensor(key)
 
     def isq_type(self, prefix: str) -> str:
-        """`isq_type_from_uqff` of the layer's serde type: the GGML dtype name for GGUF layers, HQQ8 / HQQ4 for HQQ layers (hqq/mod.rs:1327-1336), MXFP4, AFQ2 .. AFQ8."""
+        """`isq_type_from_uqff` of the layer's serde type: the GGML dtype name for GGUF layers, HQQ8 / HQQ4 for HQQ layers (hqq/mod.rs:1327-1336), MXFP4, AFQ2 .. AFQ8, F8E4M3."""
         t = self.serde_type(prefix)
         if t == SERDE_GGUF:
             return GgmlDType.from_id(self.load_u32_scalar(f"{prefix}.weight.dtype")).name
@@ -443,4 +495,6 @@ class UqffReader:
             if bits not in (2, 3, 4, 6, 8):
                 raise ValueError(f"Invalid AFQ bits {bits}.")
             return f"AFQ{bits}"
+        if t == SERDE_FP8:  # isq_type_from_uqff (fp8/mod.rs:350-352)
+            return "F8E4M3"
         raise ValueError(f"serde type {t} has no reader here")
