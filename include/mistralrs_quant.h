@@ -322,6 +322,37 @@ int launch_awq_repack(const void *qweight, const void *qzeros, void *qweight_out
                       int bits, void *stream);
 int gptq_last_route(void);
 
+/* ---- bitsandbytes blockwise formats (BnbLinear: NF4 / FP4 checkpoints, optional double-quantized absmax).  4-bit: A holds the flat tensor two elements per
+ *      byte, element 2 i in the HIGH nibble; block b covers flat elements [b * blocksize, (b + 1) * blocksize), blocksize a power of two in [64, 4096];
+ *      out[i] = RNE_T(f32(table[q_i] * absmax[i / blocksize])) with the built-in NF4 / FP4 table (`code` is ignored, as in the reference; FP4 code 8 gives -0.0).
+ *      int8: one code per byte, out[i] = RNE_T(f32(code[A[i]] * absmax[i / blocksize])) with the caller's 256-entry f32 `code`.  `n` counts OUTPUT elements; a
+ *      partial last block and an odd n are handled and nothing past n is written.  The stream slot is a hipStream_t (void * here).
+ *      replaces kernels/bitsandbytes/dequant.cu ; Rust: src/bitsandbytes/ffi.rs ; caller bitsandbytes/op.rs */
+#define MRS_BNB_DECL(T, tag)                                                                                                                        \
+  void dequantize_blockwise_##tag##_int8(const float *code, const uint8_t *A, const float *absmax, T *out, int blocksize, int n, void *stream);     \
+  void dequantize_blockwise_##tag##_fp4(const float *code, const uint8_t *A, const float *absmax, T *out, int blocksize, int n, void *stream);      \
+  void dequantize_blockwise_##tag##_nf4(const float *code, const uint8_t *A, const float *absmax, T *out, int blocksize, int n, void *stream);
+MRS_BNB_DECL(float, f32)
+MRS_BNB_DECL(uint16_t, f16)
+MRS_BNB_DECL(uint16_t, bf16)
+#undef MRS_BNB_DECL
+/* MI355X-native additions (not in the reference ABI; its forward dequantizes the whole weight and calls a library matmul), csrc/bnb.hip.  qtype: 0 int8,
+ * 1 fp4, 2 nf4 (the reference's DataType_t); dtype: 0 f32, 1 f16, 2 bf16.  nested_absmax == NULL: `absmax` is f32.  Otherwise `absmax` is u8 and the absmax of
+ * block b is f32(f32(nested_quant_map[absmax[b]] * nested_absmax[b / nested_blocksize]) + nested_offset), computed inside the kernels (4-bit types only).
+ * Each returns 0, or -1 for arguments outside the kernels (-2 / -3: launch too large / launch error).
+ *   launch_bnb_dequantize  out[i], i < n, as above; one launch with or without double quantization.
+ *   launch_bnb_matmul      y [M][N] = RNE_T(sum_k f32(x[m][k]) f32(W_hat[n][k]) + f32(bias[n])), W_hat the dequantized [N][K] weight (fp4 / nf4), f32
+ *                          accumulation, one rounding; x, bias (may be NULL) and y are `dtype`.  `workspace`: bnb_matmul_workspace_floats(M, N, K) floats on the
+ *                          device (may be NULL when that is 0) for the f32 partials of a K-split GEMV.
+ *   bnb_last_route         the route of the last matmul of this process -- 1 streaming GEMV (M <= 8, K % blocksize == 0), 2 MFMA tile (M > 8, f16 / bf16,
+ *                          K % blocksize == 0), 3 general; see csrc/bnb.hip */
+int launch_bnb_dequantize(const void *weight, const void *absmax, const float *code, const float *nested_absmax, const float *nested_quant_map, void *out,
+                          long long n, int blocksize, int nested_blocksize, float nested_offset, int qtype, int dtype, void *stream);
+int launch_bnb_matmul(const void *x, const void *weight, const void *absmax, const float *nested_absmax, const float *nested_quant_map, const void *bias, void *y,
+                      float *workspace, int M, int N, int K, int blocksize, int nested_blocksize, float nested_offset, int qtype, int dtype, void *stream);
+long long bnb_matmul_workspace_floats(int M, int N, int K);
+int bnb_last_route(void);
+
 /* ---- per-tensor FP8 (OCP E4M3FN bytes + ONE f32 scale per tensor): FP8Linear (`--isq fp8`, UQFF serde type 3) and PerTensorFP8Linear (HF `quant_method: fp8`
  *      with `weight_block_size: null`).  fp8 -> T is exact (0x7f / 0xff give NaN); T -> fp8 is e4m3_satfinite_rne(f16_rne(clamp(f32(v), +-448))).
  *      The six scalar conversions have the signatures of src/scalar_fp8/ffi.rs; the stream slot is a hipStream_t (void * here).

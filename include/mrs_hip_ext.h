@@ -179,6 +179,13 @@ int mrs_gptq_reconstruct(const void *qweight, const void *qzeros, const void *sc
 int mrs_awq_repack(const void *qweight, const void *qzeros, void *qweight_out, void *qzeros_out, void *g_idx_out, int K, int N, int groups, int group_size, int bits,
                    void *stream);
 
+/* bitsandbytes NF4 / FP4 (format and arithmetic in include/mistralrs_quant.h and csrc/bnb.hip), stream-taking entry points (ext_bnb.hip).  Arguments as
+ * launch_bnb_dequantize / launch_bnb_matmul.  Each returns 0, or < 0 for arguments outside the kernels. */
+int mrs_bnb_dequantize(const void *weight, const void *absmax, const float *code, const float *nested_absmax, const float *nested_quant_map, void *out, long long n,
+                       int blocksize, int nested_blocksize, float nested_offset, int qtype, int dtype, void *stream);
+int mrs_bnb_matmul(const void *x, const void *weight, const void *absmax, const float *nested_absmax, const float *nested_quant_map, const void *bias, void *y,
+                   float *workspace, int M, int N, int K, int blocksize, int nested_blocksize, float nested_offset, int qtype, int dtype, void *stream);
+
 /* Per-tensor FP8 (format and arithmetic in include/mistralrs_quant.h and csrc/fp8_pertensor.hip), stream-taking entry points (ext_fp8.hip) that pick the typed
  * launcher by `dtype`: 0 f32, 1 f16, 2 bf16 (the source of a quantizer, the destination of dequantize, the output and bias type of the matmul: 1 or 2 only).
  * Arguments as launch_fp8_pertensor_{quantize_dynamic,quantize_static,dequantize,matmul}_<tag>.  Each returns 0, or < 0 for arguments outside the kernels. */

@@ -264,35 +264,40 @@ class BlockwiseFP8Linear:
 
     def apply_isq(self, dtype, imatrix_weight=None):
         """mod.rs:501-670: dequantize, then hand the dense weight to the target's quantizer.  `dtype`: a GgmlDType, "HQQ4" / "HQQ8", "MXFP4", or None."""
-        from . import hqq, isq, mxfp4
-        from .gguf.matmul import GgufMatMul
-        from .gguf.qtensor import GgmlDType
         if self.weight.dim() != 2:
             raise ValueError(f"Blockwise FP8 apply_isq expects a rank-2 weight, got {list(self.weight.shape)}")
-        weight = self.dequantize_w()
-        if dtype in ("HQQ4", "HQQ8"):
-            if imatrix_weight is not None:
-                raise ValueError("HQQ does not support imatrix.")
-            cfg = hqq.HqqConfig(bits=int(dtype[3:]), group_size=HQQ_ISQ_GROUP_SIZE, axis=0, optimization_steps=hqq.OPTIMIZER_HQQ_DEFAULT_STEPS, round_zeros=False,
-                                channel_wise=True)
-            res = hqq.HqqLayer.quantize(weight, cfg)
-            return res if self.bias is None else res.with_bias(self.bias.to(res.scales.dtype))
-        if dtype == "MXFP4":
-            if imatrix_weight is not None:
-                raise ValueError("MXFP4 does not support imatrix.")
-            return mxfp4.MXFP4Layer.quantize(weight, self.bias)
-        if dtype is None:
-            return UnquantLinear(weight, self.bias)  # the imatrix is ignored altogether
-        if isinstance(dtype, GgmlDType):
-            target = isq.get_quantization_behaviour(weight.shape, dtype)
-            if target is None:
-                raise ValueError(f"isq: no GGML type fits a weight of shape {list(weight.shape)} for {dtype.name}")
-            if imatrix_weight is not None and isq.imatrix_capable(target):
-                q = isq.quantize_imatrix(weight, imatrix_weight, target)
-            else:
-                q = isq.quantize(weight, target)
-            return GgufMatMul(q, None if self.bias is None else self.bias.to(torch.float32))
-        raise ValueError(f"Blockwise FP8 apply_isq: unsupported ISQ type {dtype!r}")
+        return isq_from_dense(self.dequantize_w(), self.bias, dtype, imatrix_weight, "Blockwise FP8")
+
+
+def isq_from_dense(weight: torch.Tensor, bias: torch.Tensor | None, dtype, imatrix_weight=None, what: str = "Blockwise FP8"):
+    """The target handling of `apply_isq` for a layer that dequantizes first (blockwise FP8, bitsandbytes): the dense [N, K] weight goes to the target's
+    quantizer.  `dtype`: a GgmlDType, "HQQ4" / "HQQ8", "MXFP4", or None (the plain dense layer; the imatrix is ignored altogether)."""
+    from . import hqq, isq, mxfp4
+    from .gguf.matmul import GgufMatMul
+    from .gguf.qtensor import GgmlDType
+    if dtype in ("HQQ4", "HQQ8"):
+        if imatrix_weight is not None:
+            raise ValueError("HQQ does not support imatrix.")
+        cfg = hqq.HqqConfig(bits=int(dtype[3:]), group_size=HQQ_ISQ_GROUP_SIZE, axis=0, optimization_steps=hqq.OPTIMIZER_HQQ_DEFAULT_STEPS, round_zeros=False,
+                            channel_wise=True)
+        res = hqq.HqqLayer.quantize(weight, cfg)
+        return res if bias is None else res.with_bias(bias.to(res.scales.dtype))
+    if dtype == "MXFP4":
+        if imatrix_weight is not None:
+            raise ValueError("MXFP4 does not support imatrix.")
+        return mxfp4.MXFP4Layer.quantize(weight, bias)
+    if dtype is None:
+        return UnquantLinear(weight, bias)
+    if isinstance(dtype, GgmlDType):
+        target = isq.get_quantization_behaviour(weight.shape, dtype)
+        if target is None:
+            raise ValueError(f"isq: no GGML type fits a weight of shape {list(weight.shape)} for {dtype.name}")
+        if imatrix_weight is not None and isq.imatrix_capable(target):
+            q = isq.quantize_imatrix(weight, imatrix_weight, target)
+        else:
+            q = isq.quantize(weight, target)
+        return GgufMatMul(q, None if bias is None else bias.to(torch.float32))
+    raise ValueError(f"{what} apply_isq: unsupported ISQ type {dtype!r}")
 
 
 # ------------------------------------------------------------------------------------------------ loader pieces (pure functions)
