@@ -140,6 +140,13 @@ int mrs_dec_mm_qkv(const void *qi_q, int type_q, int nq, const void *qi_k, int t
  * dequantize_w(); the dequantized values are bit-identical to dequantize_{4,8}bit_u8_kernel_*.  -1 = outside the fused kernel (keep dequantize + dense matmul). */
 int mrs_hqq_gemv(int bits, int dtype, const void *wq, const void *scale, const void *zero, const void *bias, const void *x, int ldx, void *out, int ldo,
                  int N, int K, int b, void *stream);
+/* Fused HQQ dequant-GEMM for prompts (ext_hqq_gemm.hip): out [M][ldo] = x [M][ldx] . W_hat^T (+ bias) from the same packed tensor on the bf16 / f16 matrix cores,
+ * f32 accumulation, the bias added in f32 before the one rounding; dtype 1 = f16, 2 = bf16.  `workspace` holds mrs_hqq_gemm_workspace_floats(N, K, M) floats (the
+ * f32 partials of a K split, summed in split order; 0 = no split, NULL allowed).  Takes the stream it is given and does not synchronise.  -1 = outside the kernel
+ * (other bit widths, N % 64, K % 16, f32, pointers not 16-byte aligned, workspace missing: keep dequantize + dense matmul). */
+int mrs_hqq_gemm(int bits, int dtype, const void *wq, const void *scale, const void *zero, const void *bias, const void *x, int ldx, void *out, int ldo,
+                 int N, int K, int M, float *workspace, void *stream);
+size_t mrs_hqq_gemm_workspace_floats(int N, int K, int M);
 /* MXFP4 rows -> f32 / f16 / bf16 (ext_mxfp4.hip): out row r [K] = the dequantized row ids[r] (r when ids is null) of blocks [*][K/2] / scales [*][K/32]; the f32
  * value table[nibble] * f32_from_bits(scale << 23) is exact and converted once.  out_dtype 0 = f32, 1 = f16, 2 = bf16.  Role: MXFP4Layer::dequantize_w and
  * embedding_forward_raw (mxfp4/mod.rs:87-103,615-707), both CPU loops in the reference.  0 on success, < 0 for arguments outside the kernel. */

@@ -3,11 +3,17 @@ HQQ C ABI of libmistralrsquant.so (`dequantize_{8,4,2,1}bit_u8_kernel_*`, `dequa
 
     layer = HqqLayer.quantize(w, HqqConfig(bits=4, group_size=64))     # axis 0, channel-wise, proximal optimiser (20 steps)
     w_hat = layer.dequantize()                                         # HIP unpack + (q - zero) * scale, shape of w
-    y     = layer.forward(x)                                           # dequantize_w + dense linear (+ bias), as the reference
+    y     = layer.forward(x)                                           # x @ W_hat^T (+ bias); last_route() names the route taken
 
 PyTorch owns the buffers and runs the quantizer's elementwise tensor algebra (load-time work, exactly the candle tensor ops the
-reference runs) and the dense matmul (a plain library GEMM, as the reference's UnquantLinear); the packed format, the packing and
-the unpack + dequantize are the HIP kernels.  No CPU fallback: tensors must live on the GPU.
+reference runs); the packed format, the packing, the unpack + dequantize and the 4 / 8-bit, group-64 forward are the HIP kernels:
+    "gemv"   <= 8 rows: the fused dequant-GEMV of csrc/ext_hqq_gemv.hip (f32 / f16 / bf16)
+    "mfma"   more rows (leading dimensions flattened, up to MFMA_MAX_ROWS), bf16 / f16 scales and zeros, N % 64 == 0, K % 16 == 0: the fused MFMA tile kernel
+             of csrc/ext_hqq_gemm.hip; x is cast to the layer's dtype, f32 accumulation, the bias joins in f32 before the one rounding; takes the current
+             stream, never synchronises, never materialises the dense weight
+    "dense"  everything else (f32 above 8 rows, 3 / 2 / 1 bit, other group sizes, a refusal of the kernels): dequantize + library matmul as the reference's
+             UnquantLinear, synchronising on a non-default stream (the reference's dequantize ABI has no stream argument)
+No CPU fallback: tensors must live on the GPU.
 """
 from __future__ import annotations
 
@@ -22,6 +28,14 @@ _PACK = {8: 1, 4: 2, 3: 10, 2: 4, 1: 8}
 _KERNEL = {8: "8bit_u8_kernel", 4: "4bit_u8_kernel", 2: "2bit_u8_kernel", 1: "1bit_u8_kernel", 3: "3bit_32_kernel"}
 _TAG = {torch.float32: "f32", torch.float16: "f16", torch.bfloat16: "bf16"}
 OPTIMIZER_HQQ_DEFAULT_STEPS = 20  # hqq/mod.rs
+MFMA_MAX_ROWS = 128      # rows above which forward() keeps dequantize + library matmul: the measured crossover, one 128-row tile
+_WORKSPACE: dict = {}    # per device: the f32 partials of a K-split prompt GEMM; grown on demand, shared by every layer (launches of one stream are ordered)
+_last_route = None
+
+
+def last_route():
+    """The route of the last `HqqLayer.forward`: "gemv" (<= 8 rows, fused), "mfma" (more rows, fused tile kernel) or "dense" (dequantize + library matmul)."""
+    return _last_route
 
 
 @dataclass(frozen=True)
@@ -176,11 +190,41 @@ class HqqLayer:
             n *= d
         return out.reshape(-1)[:n].reshape(self.w_shape)  # 3 bit: ten values per i32 may over-cover the group rows
 
+    def _forward_mfma(self, xs: torch.Tensor):
+        """The fused prompt GEMM of csrc/ext_hqq_gemm.hip, or None when the layer, the input or the symbol is outside it."""
+        dt = self.scales.dtype
+        if not (self.cfg.bits in (4, 8) and self.cfg.group_size == 64 and self.cfg.axis == 0 and len(self.w_shape) == 2 and dt in (torch.float16, torch.bfloat16)
+                and self.zeros.dtype == dt and xs.dim() >= 2 and self.w_shape[0] % 64 == 0 and self.w_shape[1] % 16 == 0 and xs.shape[-1] == self.w_shape[1]):
+            return None
+        n, k = self.w_shape
+        m = xs.numel() // k
+        if not 8 < m <= MFMA_MAX_ROWS:
+            return None
+        _need_gpu(xs)
+        x = xs.to(dt).reshape(m, k).contiguous()
+        out = torch.empty(m, n, dtype=dt, device=x.device)
+        bias = self.bias.to(dt).contiguous() if self.bias is not None else None
+        floats = int(_lib.sym("ext", "mrs_hqq_gemm_workspace_floats", [C.c_int] * 3, C.c_size_t)(n, k, m))
+        ws = _WORKSPACE.get(x.device)
+        if floats and (ws is None or ws.numel() < floats):
+            ws = _WORKSPACE[x.device] = torch.empty(floats, dtype=torch.float32, device=x.device)
+        fn = _lib.sym("ext", "mrs_hqq_gemm", [C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p], C.c_int)
+        rc = fn(self.cfg.bits, 1 if dt == torch.float16 else 2, self.w_q.data_ptr(), self.scales.data_ptr(), self.zeros.data_ptr(),
+                bias.data_ptr() if bias is not None else None, x.data_ptr(), k, out.data_ptr(), n, n, k, m, ws.data_ptr() if floats else None,
+                torch.cuda.current_stream().cuda_stream)
+        return out.reshape(*xs.shape[:-1], n) if rc == 0 else None
+
     def forward(self, xs: torch.Tensor) -> torch.Tensor:
         """HqqLayer::forward_raw (mod.rs:1092-1100,1163-1171): x @ W^T (+ bias).  Decode-sized inputs (<= 8 rows, 4 / 8 bit, group 64) take the fused
-        dequant-GEMV of csrc/ext_hqq_gemv.hip (the packed bytes are read once, dequantize_w() is never materialised); everything else dequantizes and
-        uses the dense matmul like the reference."""
+        dequant-GEMV of csrc/ext_hqq_gemv.hip (the packed bytes are read once, dequantize_w() is never materialised); more rows of a bf16 / f16 layer take
+        the fused MFMA tile kernel of csrc/ext_hqq_gemm.hip; everything else dequantizes and uses the dense matmul like the reference."""
+        global _last_route
         dt = self.scales.dtype
+        y = self._forward_mfma(xs)
+        if y is not None:
+            _last_route = "mfma"
+            return y
+        _last_route = "dense"
         if (self.cfg.bits in (4, 8) and self.cfg.group_size == 64 and self.cfg.axis == 0 and xs.dim() == 2 and 1 <= xs.shape[0] <= 8 and len(self.w_shape) == 2
                 and self.w_shape[0] % 64 == 0 and self.w_shape[1] % 4 == 0 and dt in _TAG and self.zeros.dtype == dt):
             _need_gpu(xs)
@@ -192,6 +236,7 @@ class HqqLayer:
             rc = fn(self.cfg.bits, {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}[dt], self.w_q.data_ptr(), self.scales.data_ptr(), self.zeros.data_ptr(),
                     bias.data_ptr() if bias is not None else None, x.data_ptr(), k, out.data_ptr(), n, n, k, x.shape[0], torch.cuda.current_stream().cuda_stream)
             if rc == 0:
+                _last_route = "gemv"
                 return out
         w = self.dequantize()
         y = xs.to(w.dtype) @ w.t()
