@@ -98,6 +98,22 @@ void update_kv_scales_f32(void *k, void *v, const long num_elements, float *k_sc
 void update_kv_scales_f16(void *k, void *v, const long num_elements, float *k_scales, float *v_scales, int64_t stream);
 void update_kv_scales_bf16(void *k, void *v, const long num_elements, float *k_scales, float *v_scales, int64_t stream);
 
+/* ffi.rs `flash_attn_sinks_*` ; flash_attn_sinks.cu: causal prompt attention with per-head sinks on dense tensors.
+ * Q, O [B, H, q_len, D]; K, V [B, Hkv, kv_len, D]; sinks f32 [H] or NULL; window_size 0 = causal only.  The mask is aligned to the
+ * bottom right: row r attends keys max(0, r + kv_len - q_len - W + 1) .. r + kv_len - q_len.  D in 64/80/96/112/128/192/256, anything
+ * else launches nothing.  varlen: Q, O padded [B, H, max_q_len, D]; K, V packed [total_kv, Hkv, D]; cu_seqlens_* u32 [B + 1]; rows
+ * past a sequence's q length are not written. */
+#define MRS_DECL_FAS(d)                                                                                                \
+  void flash_attn_sinks_##d(const void *Q, const void *K, const void *V, void *O, const float *sinks, float scale,     \
+                            int batch_size, int q_len, int kv_len, int num_heads, int num_kv_heads, int head_dim,      \
+                            int window_size, void *stream);                                                            \
+  void flash_attn_sinks_varlen_##d(const void *Q, const void *K, const void *V, void *O, const float *sinks,           \
+                                   const unsigned *cu_seqlens_q, const unsigned *cu_seqlens_k, float scale,            \
+                                   int batch_size, int max_q_len, int num_heads, int num_kv_heads, int head_dim,       \
+                                   int window_size, void *stream);
+MRS_DECL_FAS(f16) MRS_DECL_FAS(bf16) MRS_DECL_FAS(f32)
+#undef MRS_DECL_FAS
+
 #ifdef __cplusplus
 }
 #endif

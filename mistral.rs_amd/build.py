@@ -51,6 +51,7 @@ def libraries():
     for tag, t in (("f16", "mrs::f16_t"), ("bf16", "mrs::bf16_t"), ("f32", "float")):  # fp8 (E4M3) cache read as query dtype `tag`
         pa.append(_tu("paged_attention.hip", f"paged_attention_{tag}_fp8.o",
                       [f"-DMRS_PA_TAG={tag}", f"-DMRS_PA_T={t}", "-DMRS_PA_CT=mrs::fp8_t", "-DMRS_PA_FP8"]))
+    pa.append(_tu("flash_attn_sinks.hip"))  # prompt attention with sinks on dense Q / K / V (flash_attn_sinks.cu)
     libs["libmistralrspagedattention.so"] = pa
     # optional translation units are picked up as soon as the file exists
     optional = {

@@ -244,6 +244,70 @@ def decode_attention_q8_1(q: torch.Tensor, key_cache: torch.Tensor, value_cache:
     return y, stride_blocks
 
 
+_SINK_HEAD_DIMS = (64, 80, 96, 112, 128, 192, 256)
+
+
+def _sinks_checks(name: str, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, sinks, kv_rank: int):
+    """Shared checks of the two ops below (backend/flash_attn_sinks.rs:26-58,184-196); returns the sinks pointer or None."""
+    if q.dtype not in _CODE:
+        raise ValueError(f"{name}: only f32 / f16 / bf16 are supported, got {q.dtype}")
+    if k.dtype != q.dtype or v.dtype != q.dtype:
+        raise ValueError(f"{name}: q, k and v must share one dtype")
+    if q.dim() != 4 or k.dim() != kv_rank or v.shape != k.shape:
+        raise ValueError(f"{name}: shape mismatch q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}")
+    if not (q.is_cuda and k.is_cuda and v.is_cuda):
+        raise ValueError(f"{name}: q, k and v must be GPU tensors")
+    if not (q.is_contiguous() and k.is_contiguous() and v.is_contiguous()):
+        raise ValueError(f"{name}: q, k and v must be contiguous")
+    num_heads, head_dim = q.shape[1], q.shape[3]
+    if head_dim not in _SINK_HEAD_DIMS:
+        raise ValueError(f"{name}: head_dim must be one of 64, 80, 96, 112, 128, 192, 256, got {head_dim}")
+    num_kv_heads = k.shape[-2] if kv_rank == 3 else k.shape[1]
+    if k.shape[-1] != head_dim or num_kv_heads == 0 or num_heads % num_kv_heads:
+        raise ValueError(f"{name}: k {tuple(k.shape)} does not match q {tuple(q.shape)}")
+    if sinks is None:
+        return None
+    if sinks.dtype != torch.float32 or tuple(sinks.shape) != (num_heads,) or not sinks.is_cuda or not sinks.is_contiguous():
+        raise ValueError(f"{name}: sinks must be a contiguous f32 GPU tensor [{num_heads}]")
+    return sinks.data_ptr()
+
+
+def flash_attn_sinks(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, sinks: torch.Tensor | None, softmax_scale: float,
+                     window_size: int) -> torch.Tensor:
+    """Causal prompt attention with per-head sinks (backend/flash_attn_sinks.rs:320 `flash_attn_sinks`): q [B, H, q_len, D],
+    k / v [B, Hkv, kv_len, D], sinks f32 [H] or None, window_size 0 = no window -> [B, H, q_len, D].  The mask is aligned to the bottom right
+    (row r sees keys up to r + kv_len - q_len); a sink adds exp(sink) to the softmax denominator and no value."""
+    sk = _sinks_checks("flash_attn_sinks", q, k, v, sinks, 4)
+    batch, num_heads, q_len, head_dim = q.shape
+    if k.shape[0] != batch:
+        raise ValueError(f"flash_attn_sinks: k {tuple(k.shape)} does not match q {tuple(q.shape)}")
+    if window_size < 0:
+        raise ValueError("flash_attn_sinks: window_size must be >= 0")
+    out = torch.empty_like(q)
+    fn = _lib.sym("paged_attn", f"flash_attn_sinks_{_TAG[q.dtype]}", [_vp] * 5 + [_f] + [_i] * 7 + [_vp])
+    fn(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), sk, softmax_scale, batch, q_len, k.shape[2], num_heads, k.shape[1], head_dim,
+       window_size, _stream())
+    return out
+
+
+def flash_attn_sinks_varlen(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, sinks: torch.Tensor | None, cu_seqlens_q: torch.Tensor,
+                            cu_seqlens_k: torch.Tensor, softmax_scale: float, window_size: int) -> torch.Tensor:
+    """Variable-length form (backend/flash_attn_sinks.rs:360 `flash_attn_sinks_varlen`): q padded [B, H, max_q_len, D], k / v packed
+    [total_kv, Hkv, D], cu_seqlens_q / cu_seqlens_k uint32 [B + 1] -> [B, H, max_q_len, D] with the padding rows zero."""
+    sk = _sinks_checks("flash_attn_sinks_varlen", q, k, v, sinks, 3)
+    batch, num_heads, max_q_len, head_dim = q.shape
+    for name, t in (("cu_seqlens_q", cu_seqlens_q), ("cu_seqlens_k", cu_seqlens_k)):
+        if t.dtype != torch.uint32 or tuple(t.shape) != (batch + 1,) or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"flash_attn_sinks_varlen: {name} must be a contiguous uint32 GPU tensor [{batch + 1}]")
+    if window_size < 0:
+        raise ValueError("flash_attn_sinks_varlen: window_size must be >= 0")
+    out = torch.zeros_like(q)
+    fn = _lib.sym("paged_attn", f"flash_attn_sinks_varlen_{_TAG[q.dtype]}", [_vp] * 7 + [_f] + [_i] * 6 + [_vp])
+    fn(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), sk, cu_seqlens_q.data_ptr(), cu_seqlens_k.data_ptr(), softmax_scale, batch,
+       max_q_len, num_heads, k.shape[1], head_dim, window_size, _stream())
+    return out
+
+
 def prefill_attention(q: torch.Tensor, key_cache: torch.Tensor, value_cache: torch.Tensor, block_table: torch.Tensor, start_pos: int,
                       softmax_scale: float) -> torch.Tensor:
     """Causal prompt attention on the matrix cores (mrs_prefill_attention_f32_bf16): f32 q [T, heads, hd] at positions
