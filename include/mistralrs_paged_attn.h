@@ -12,6 +12,7 @@
  */
 #ifndef MISTRALRS_PAGED_ATTN_H
 #define MISTRALRS_PAGED_ATTN_H
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -113,6 +114,36 @@ void update_kv_scales_bf16(void *k, void *v, const long num_elements, float *k_s
                                    int window_size, void *stream);
 MRS_DECL_FAS(f16) MRS_DECL_FAS(bf16) MRS_DECL_FAS(f32)
 #undef MRS_DECL_FAS
+
+/* Multi-head latent attention (DeepSeek-V2 / V3) on a paged latent cache; dtype 0 = f16, 1 = bf16, 2 = f32 (cache ops only).
+ *   ckv_cache [num_blocks, block_size, kv_lora_rank]   kpe_cache [num_blocks, block_size, kpe_head_dim]
+ * ffi.rs:118-132 ; concat_and_cache_mla_kernel.cu: token i goes to slot slot_mapping[i] (int64; < 0 is skipped); ckv_stride / kpe_stride are
+ * the input row strides in elements. */
+void concat_and_cache_mla(const void *ckv, const void *k_pe, void *ckv_cache, void *kpe_cache, const int64_t *slot_mapping,
+                          int num_tokens, int kv_lora_rank, int kpe_head_dim, int block_size, int ckv_stride, int kpe_stride,
+                          mrs_stream_t stream, uint32_t dtype);
+/* ffi.rs:231-246 ; gather_mla_cache_kernel.cu: paged -> dense [num_tokens, kv_lora_rank] / [num_tokens, kpe_head_dim]; token i is position
+ * i - cu_seq_lens[s] of sequence s = token_to_seq[i], in block block_table[s * block_table_stride + position / block_size]. */
+void gather_mla_cache(const void *ckv_cache, const void *kpe_cache, void *ckv_out, void *kpe_out, const int *block_table,
+                      const int *cu_seq_lens, const int *token_to_seq, int num_tokens, int block_size, int block_table_stride,
+                      int kv_lora_rank, int kpe_head_dim, mrs_stream_t stream, uint32_t dtype);
+/* ffi.rs:134-157: one query token per request over kv_lora_rank 512 / kpe_head_dim 64, f16 or bf16, page_size 16 or 32.
+ * q_nope [batch, heads, 512], q_pe [batch, heads, 64], out [batch, heads, 512]; request b owns pages
+ * kv_indices[kv_indptr[b] .. kv_indptr[b + 1]) and (pages - 1) * page_size + kv_last_page_len[b] keys (none without a page: zeros).
+ * Returns 0, or non-zero for f32 (no kernel: stated deviation), another page size, window_left >= 0 or logits_soft_cap != 0.  The four tile-plan
+ * pointers and rope_scale / rope_theta are not read (Q and K arrive rotated); without a workspace this entry runs one KV split. */
+int flashinfer_mla_decode(const void *q_nope, const void *q_pe, const void *ckv_cache, const void *kpe_cache, const int *kv_indptr,
+                          const int *kv_indices, const int *kv_last_page_len, void *out, int batch_size, int num_qo_heads,
+                          int page_size, float sm_scale, int window_left, float logits_soft_cap, float rope_scale, float rope_theta,
+                          const int *request_indices, const int *kv_tile_indices, const int *o_indptr, const int *kv_chunk_size_ptr,
+                          uint32_t dtype, mrs_stream_t stream);
+/* MI355X-native: the same decode with the context split num_splits ways over the grid (batch, head blocks, num_splits) and merged by a second
+ * small launch; lengths are read on the device only, so the call can be captured in a graph.  workspace: f32, 16-byte aligned, at least
+ * mla_decode_workspace_bytes(batch_size, num_qo_heads, num_splits) bytes (0 for one split, which writes the output with one launch). */
+size_t mla_decode_workspace_bytes(int batch_size, int num_qo_heads, int num_splits);
+int launch_mla_decode(const void *q_nope, const void *q_pe, const void *ckv_cache, const void *kpe_cache, const int *kv_indptr,
+                      const int *kv_indices, const int *kv_last_page_len, void *out, int batch_size, int num_qo_heads, int page_size,
+                      float sm_scale, int num_splits, void *workspace, size_t workspace_bytes, uint32_t dtype, mrs_stream_t stream);
 
 #ifdef __cplusplus
 }

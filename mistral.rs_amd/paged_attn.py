@@ -308,6 +308,118 @@ def flash_attn_sinks_varlen(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, s
     return out
 
 
+_MLA_DIMS = (512, 64)  # kv_lora_rank, rotary head dim: what the decode kernel is built for (backend/mla.rs:262)
+_MLA_CUS = 256         # compute units of the MI355X, one decode workgroup each
+
+
+def _mla_caches(name: str, ckv_cache: torch.Tensor, kpe_cache: torch.Tensor, dtype):
+    """Shared cache checks of the three MLA ops (backend/mla.rs:25-31,66-84,659-663); returns (block_size, kv_lora_rank, kpe_head_dim)."""
+    if dtype not in _CODE:
+        raise ValueError(f"{name}: only f16 / bf16 / f32 are supported, got {dtype}")
+    if ckv_cache.dtype != dtype or kpe_cache.dtype != dtype:
+        raise ValueError(f"{name}: cache dtypes {ckv_cache.dtype} / {kpe_cache.dtype} do not match {dtype}")
+    if ckv_cache.dim() != 3 or kpe_cache.dim() != 3 or ckv_cache.shape[:2] != kpe_cache.shape[:2]:
+        raise ValueError(f"{name}: block shape mismatch ckv_cache {tuple(ckv_cache.shape)} and kpe_cache {tuple(kpe_cache.shape)}")
+    if not (ckv_cache.is_cuda and kpe_cache.is_cuda and ckv_cache.is_contiguous() and kpe_cache.is_contiguous()):
+        raise ValueError(f"{name}: the caches must be contiguous GPU tensors")
+    return ckv_cache.shape[1], ckv_cache.shape[2], kpe_cache.shape[2]
+
+
+def _mla_meta(name: str, what: str, t: torch.Tensor, numel: int | None = None) -> torch.Tensor:
+    if t.dtype != torch.int32 or t.dim() != 1 or not t.is_cuda or (numel is not None and t.numel() != numel):
+        raise ValueError(f"{name}: {what} must be an int32 GPU vector" + ("" if numel is None else f" of length {numel}") + f", got {t.dtype} {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def concat_and_cache_mla(ckv: torch.Tensor, k_pe: torch.Tensor, ckv_cache: torch.Tensor, kpe_cache: torch.Tensor, slot_mapping: torch.Tensor) -> None:
+    """Write one latent row and one rotary row per token into the paged MLA cache (backend/mla.rs:10 `concat_and_cache_mla`): ckv [T, kv_lora_rank],
+    k_pe [T, kpe_head_dim] (row strides may exceed the row), caches [num_blocks, block_size, rank / dim], slot_mapping int64 [T]; negative slots are skipped."""
+    name = "concat_and_cache_mla"
+    if k_pe.dtype != ckv.dtype:
+        raise ValueError(f"{name}: ckv and k_pe must share one dtype, got {ckv.dtype} and {k_pe.dtype}")
+    block_size, rank, pe_dim = _mla_caches(name, ckv_cache, kpe_cache, ckv.dtype)
+    if ckv.dim() != 2 or k_pe.dim() != 2 or ckv.shape[0] != k_pe.shape[0] or ckv.shape[1] != rank or k_pe.shape[1] != pe_dim:
+        raise ValueError(f"{name}: shape mismatch ckv {tuple(ckv.shape)}, k_pe {tuple(k_pe.shape)}, caches {tuple(ckv_cache.shape)} / {tuple(kpe_cache.shape)}")
+    if not (ckv.is_cuda and k_pe.is_cuda) or ckv.stride(1) != 1 or k_pe.stride(1) != 1:
+        raise ValueError(f"{name}: ckv and k_pe must be GPU tensors with contiguous rows")
+    num_tokens = ckv.shape[0]
+    if slot_mapping.dtype != torch.int64 or slot_mapping.dim() != 1 or slot_mapping.numel() != num_tokens or not slot_mapping.is_cuda:
+        raise ValueError(f"{name}: slot_mapping must be an int64 GPU vector of length {num_tokens}")
+    fn = _lib.sym("paged_attn", "concat_and_cache_mla", [_vp] * 5 + [_i] * 6 + [_vp, _u])
+    fn(ckv.data_ptr(), k_pe.data_ptr(), ckv_cache.data_ptr(), kpe_cache.data_ptr(), slot_mapping.contiguous().data_ptr(), num_tokens, rank, pe_dim,
+       block_size, ckv.stride(0), k_pe.stride(0), _stream(), _CODE[ckv.dtype])
+
+
+def gather_mla_cache(ckv_cache: torch.Tensor, kpe_cache: torch.Tensor, block_table: torch.Tensor, cu_seq_lens: torch.Tensor,
+                     token_to_seq: torch.Tensor):
+    """Paged MLA cache -> dense (ckv [T, kv_lora_rank], kpe [T, kpe_head_dim]) (backend/mla.rs:643 `gather_mla_cache`): token i is position
+    i - cu_seq_lens[s] of sequence s = token_to_seq[i]; block_table int32 [seqs, max_blocks], cu_seq_lens int32 [seqs + 1], token_to_seq int32 [T]."""
+    name = "gather_mla_cache"
+    block_size, rank, pe_dim = _mla_caches(name, ckv_cache, kpe_cache, ckv_cache.dtype)
+    if block_table.dtype != torch.int32 or block_table.dim() != 2 or not block_table.is_cuda:
+        raise ValueError(f"{name}: block_table must be an int32 GPU matrix, got {block_table.dtype} {tuple(block_table.shape)}")
+    block_table = block_table.contiguous()
+    cu_seq_lens = _mla_meta(name, "cu_seq_lens", cu_seq_lens, block_table.shape[0] + 1)
+    token_to_seq = _mla_meta(name, "token_to_seq", token_to_seq)
+    num_tokens = token_to_seq.numel()
+    ckv = torch.zeros(num_tokens, rank, dtype=ckv_cache.dtype, device=ckv_cache.device)
+    kpe = torch.zeros(num_tokens, pe_dim, dtype=ckv_cache.dtype, device=ckv_cache.device)
+    fn = _lib.sym("paged_attn", "gather_mla_cache", [_vp] * 7 + [_i] * 5 + [_vp, _u])
+    fn(ckv_cache.data_ptr(), kpe_cache.data_ptr(), ckv.data_ptr(), kpe.data_ptr(), block_table.data_ptr(), cu_seq_lens.data_ptr(),
+       token_to_seq.data_ptr(), num_tokens, block_size, block_table.stride(0), rank, pe_dim, _stream(), _CODE[ckv_cache.dtype])
+    return ckv, kpe
+
+
+def mla_decode_splits(batch: int, num_heads: int, max_kv_len: int) -> int:
+    """KV splits for `flashinfer_mla_decode` from host-known quantities: enough workgroups (batch x head blocks x splits) to cover the compute units,
+    but no split shorter than 16 tiles of 32 keys for a 64-head block, 8 for a 32-head one: a split's f32 partial (2 KiB per head, written and read
+    back) then stays under half of the 36 KiB per tile that it reads."""
+    groups = max(1, batch * (-(-num_heads // 64)))
+    tiles = -(-max(max_kv_len, 1) // 32)
+    return max(1, min(_MLA_CUS // groups, tiles // (16 if num_heads > 32 else 8), 128))
+
+
+def flashinfer_mla_decode(q_nope: torch.Tensor, q_pe: torch.Tensor, ckv_cache: torch.Tensor, kpe_cache: torch.Tensor, paged_kv_indptr: torch.Tensor,
+                          paged_kv_indices: torch.Tensor, paged_kv_last_page_len: torch.Tensor, sm_scale: float, *, num_splits: int | None = None,
+                          max_kv_len: int | None = None) -> torch.Tensor:
+    """MLA decode over the paged latent cache (backend/mla.rs:227 `flashinfer_mla_decode`): q_nope [batch, heads, 512], q_pe [batch, heads, 64] (rotated),
+    caches [num_blocks, page_size, 512 / 64] with page_size 16 or 32, f16 or bf16; request b owns pages paged_kv_indices[indptr[b] : indptr[b + 1]] with
+    paged_kv_last_page_len[b] keys in the last one -> [batch, heads, 512]; a request without keys gets zeros.  num_splits None picks the split count
+    from batch, head blocks and max_kv_len (default: paged_kv_indices.numel() * page_size, an upper bound); nothing is read back from the device."""
+    name = "flashinfer_mla_decode"
+    if q_pe.dtype != q_nope.dtype:
+        raise ValueError(f"{name}: q_nope and q_pe must share one dtype, got {q_nope.dtype} and {q_pe.dtype}")
+    if q_nope.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"{name}: only f16 / bf16 are supported, got {q_nope.dtype}")
+    page_size, rank, pe_dim = _mla_caches(name, ckv_cache, kpe_cache, q_nope.dtype)
+    if q_nope.dim() != 3 or q_pe.dim() != 3 or q_nope.shape[:2] != q_pe.shape[:2]:
+        raise ValueError(f"{name}: shape mismatch q_nope {tuple(q_nope.shape)} and q_pe {tuple(q_pe.shape)}")
+    batch, num_heads = q_nope.shape[:2]
+    if (q_nope.shape[2], q_pe.shape[2]) != _MLA_DIMS or (rank, pe_dim) != _MLA_DIMS:
+        raise ValueError(f"{name}: head dims must be 512 / 64, got q {q_nope.shape[2]} / {q_pe.shape[2]}, caches {rank} / {pe_dim}")
+    if page_size not in (16, 32):
+        raise ValueError(f"{name}: page size must be 16 or 32, got {page_size}")
+    if num_heads < 1 or not (q_nope.is_cuda and q_pe.is_cuda and q_nope.is_contiguous() and q_pe.is_contiguous()):
+        raise ValueError(f"{name}: q_nope and q_pe must be contiguous GPU tensors with at least one head")
+    indptr = _mla_meta(name, "paged_kv_indptr", paged_kv_indptr, batch + 1)
+    last = _mla_meta(name, "paged_kv_last_page_len", paged_kv_last_page_len, batch)
+    indices = _mla_meta(name, "paged_kv_indices", paged_kv_indices)
+    if num_splits is None:
+        num_splits = mla_decode_splits(batch, num_heads, indices.numel() * page_size if max_kv_len is None else max_kv_len)
+    if num_splits < 1:
+        raise ValueError(f"{name}: num_splits must be >= 1")
+    out = torch.empty_like(q_nope)
+    nbytes = _lib.sym("paged_attn", "mla_decode_workspace_bytes", [_i] * 3, C.c_size_t)(batch, num_heads, num_splits)
+    ws = _workspace(q_nope.device, nbytes) if nbytes else None
+    fn = _lib.sym("paged_attn", "launch_mla_decode", [_vp] * 8 + [_i] * 3 + [_f, _i, _vp, C.c_size_t, _u, _vp], _i)
+    rc = fn(q_nope.data_ptr(), q_pe.data_ptr(), ckv_cache.data_ptr(), kpe_cache.data_ptr(), indptr.data_ptr(), indices.data_ptr(), last.data_ptr(),
+            out.data_ptr(), batch, num_heads, page_size, sm_scale, num_splits, None if ws is None else ws.data_ptr(), nbytes, _CODE[q_nope.dtype],
+            _stream())
+    if rc != 0:
+        raise RuntimeError(f"{name}: launch_mla_decode returned {rc}")
+    return out
+
+
 def prefill_attention(q: torch.Tensor, key_cache: torch.Tensor, value_cache: torch.Tensor, block_table: torch.Tensor, start_pos: int,
                       softmax_scale: float) -> torch.Tensor:
     """Causal prompt attention on the matrix cores (mrs_prefill_attention_f32_bf16): f32 q [T, heads, hd] at positions
