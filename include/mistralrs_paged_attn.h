@@ -145,6 +145,37 @@ int launch_mla_decode(const void *q_nope, const void *q_pe, const void *ckv_cach
                       const int *kv_indices, const int *kv_last_page_len, void *out, int batch_size, int num_qo_heads, int page_size,
                       float sm_scale, int num_splits, void *workspace, size_t workspace_bytes, uint32_t dtype, mrs_stream_t stream);
 
+/* GQA decode over an HND paged cache (the reference's FlashInfer back end, flashinfer_decode.cu / backend/flashinfer.rs); codes as above.
+ *   key_cache / value_cache [num_pages, kv_heads, page_size, head_size]; an E4M3 cache (cache_dtype 3) holds value / scale, scales passed by value.
+ * Token i goes to slot slot_mapping[i] (int64; < 0 is skipped): element (h, d) lands at ((slot / bs * H + h) * bs + slot % bs) * D + d.
+ * key_stride / value_stride are the input row strides in elements.  dtype f16 / bf16 / f32, cache_dtype the same or 3. */
+void reshape_and_cache_flashinfer(void *key, void *value, void *key_cache, void *value_cache, int64_t *slot_mapping, int32_t num_tokens,
+                                  int32_t num_heads, int32_t head_size, int32_t block_size, int32_t key_stride, int32_t value_stride,
+                                  float k_scale, float v_scale, uint32_t dtype, uint32_t cache_dtype, mrs_stream_t stream);
+/* paged -> dense [num_tokens, kv_heads, head_size]; token i is position i - cu_seq_lens[s] of the sequence s with cu_seq_lens[s] <= i < cu_seq_lens[s + 1]
+ * (binary search), in page block_table[s * block_table_stride + position / block_size].  E4M3 pages come back as float(code) * scale. */
+void gather_kv_cache_flashinfer(void *key_cache, void *value_cache, void *k_out, void *v_out, const int32_t *block_table,
+                                const int32_t *cu_seq_lens, int32_t num_tokens, int32_t num_seqs, int32_t block_size,
+                                int32_t block_table_stride, int32_t num_kv_heads, int32_t head_size, uint32_t out_dtype, uint32_t cache_dtype,
+                                float k_scale, float v_scale, mrs_stream_t stream);
+/* One query token per request; q [batch, heads, head_size] with element strides q_stride_n / q_stride_h, o [batch, heads, head_size] contiguous.
+ * Request b owns pages kv_indices[kv_indptr[b] .. kv_indptr[b + 1]) and (pages - 1) * page_size + kv_last_page_len[b] keys (none without a page: zeros).
+ * Grid entry bx < padded_batch_size does nothing when block_valid_mask[bx] == 0 (one byte each, the reference's bool); otherwise it serves request
+ * request_indices[bx], keys [t c, (t + 1) c) with t = kv_tile_indices[bx], c = *kv_chunk_size_ptr (read on the device; a multiple of page_size), and
+ * writes partial row o_indptr[b] + t; a second launch merges rows o_indptr[b] .. o_indptr[b + 1] in index order.  With tmp_v == NULL the KV is not
+ * partitioned: the entry with t == 0 covers all keys of its request.  window_left < 0: no window, else key i is visible iff
+ * i + 1 + window_left >= kv_len; logits_soft_cap <= 0: no cap.  DEVIATION from the reference: tmp_v is F32 [padded_batch_size, heads, head_size]
+ * (there: the query dtype), so a split adds no rounding; tmp_s f32 [padded_batch_size, heads] holds the log-sum-exp.  All pointers 16-byte aligned
+ * except q (2).  Returns 0, or non-zero WITHOUT launching for what it does not serve: f32 queries (1), a cache dtype that is neither the query's
+ * nor E4M3 (2), head_size other than 64 / 128 / 256 (3), page_size other than 16 / 32 (4), heads not a multiple of kv_heads or more than 16 heads
+ * per KV head (5), bad scratch or alignment (6); 7 is a failed launch. */
+int32_t flashinfer_decode(void *q, void *key_cache, void *value_cache, const int32_t *kv_indptr, const int32_t *kv_indices,
+                          const int32_t *kv_last_page_len, const int32_t *request_indices, const int32_t *kv_tile_indices,
+                          const int32_t *o_indptr, const int32_t *kv_chunk_size_ptr, const uint8_t *block_valid_mask, void *o, void *tmp_v,
+                          void *tmp_s, int32_t batch_size, int32_t padded_batch_size, int32_t num_qo_heads, int32_t num_kv_heads,
+                          int32_t head_size, int32_t page_size, int32_t q_stride_n, int32_t q_stride_h, float sm_scale, int32_t window_left,
+                          float logits_soft_cap, float k_scale, float v_scale, uint32_t dtype, uint32_t cache_dtype, mrs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

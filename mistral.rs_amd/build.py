@@ -53,6 +53,7 @@ def libraries():
                       [f"-DMRS_PA_TAG={tag}", f"-DMRS_PA_T={t}", "-DMRS_PA_CT=mrs::fp8_t", "-DMRS_PA_FP8"]))
     pa.append(_tu("flash_attn_sinks.hip"))  # prompt attention with sinks on dense Q / K / V (flash_attn_sinks.cu)
     pa.append(_tu("mla.hip"))  # MLA latent-cache ops and paged decode (concat_and_cache_mla_kernel.cu, gather_mla_cache_kernel.cu, flashinfer_mla_decode)
+    pa.append(_tu("flashinfer_decode.hip"))  # HND-cache ops and GQA decode by a tile plan (flashinfer_decode.cu)
     libs["libmistralrspagedattention.so"] = pa
     # optional translation units are picked up as soon as the file exists
     optional = {

@@ -8,6 +8,8 @@ C ABI of libmistralrspagedattention.so on the caller's current stream.
 from __future__ import annotations
 
 import ctypes as C
+import math
+from typing import NamedTuple
 
 import torch
 
@@ -417,6 +419,193 @@ def flashinfer_mla_decode(q_nope: torch.Tensor, q_pe: torch.Tensor, ckv_cache: t
             _stream())
     if rc != 0:
         raise RuntimeError(f"{name}: launch_mla_decode returned {rc}")
+    return out
+
+
+# ---------------------------------------------------------------------------------- FlashInfer-layout (HND) cache, CSR requests, tile plan
+_FI_HEAD_SIZES = (64, 128, 256)  # what the decode kernel is built for; 512 is refused (deviations)
+_FI_CUS = 256                    # compute units of the MI355X
+
+
+class FlashInferDecodePlan(NamedTuple):
+    """The split-KV tile plan of `flashinfer_decode`: int32 [padded], int32 [padded], int32 [batch + 1], int32 [1], uint8 [padded]."""
+    request_indices: torch.Tensor
+    kv_tile_indices: torch.Tensor
+    o_indptr: torch.Tensor
+    kv_chunk_size: torch.Tensor
+    block_valid_mask: torch.Tensor
+
+
+def flashinfer_cache_shape(num_blocks: int, num_kv_heads: int, head_size: int, block_size: int):
+    """K and V caches of the FlashInfer path share one shape, [num_pages, kv_heads, page_size, head_size] (HND): a key row is head_size contiguous
+    elements.  Neither cache can be read by `paged_attention` (x-packed K, transposed V: `kv_cache_shapes`), nor the reverse."""
+    return (num_blocks, num_kv_heads, block_size, head_size)
+
+
+def _fi_cache(name: str, dtype, key_cache: torch.Tensor, value_cache: torch.Tensor, k_scale: float, v_scale: float):
+    """validate_cache_dtype / validate_cache_scales and the cache shape checks of backend/flashinfer.rs:35-62,109-112; returns the cache dtype code."""
+    if dtype not in _CODE:
+        raise ValueError(f"{name} only supports f16, bf16, f32 (got {dtype})")
+    if key_cache.dtype not in _CACHE_CODE or value_cache.dtype != key_cache.dtype:
+        raise ValueError(f"{name} expects matching cache dtypes out of f16, bf16, f32, f8e4m3 (got {key_cache.dtype}, {value_cache.dtype})")
+    code = _CACHE_CODE[key_cache.dtype]
+    if code != 3 and key_cache.dtype != dtype:
+        raise ValueError(f"{name} requires matching activation/cache dtypes or an f8e4m3 cache, got activation={dtype}, cache={key_cache.dtype}")
+    if not (math.isfinite(k_scale) and k_scale > 0.0 and math.isfinite(v_scale) and v_scale > 0.0):
+        raise ValueError(f"{name} requires finite positive K/V cache scales, got k={k_scale} v={v_scale}")
+    if code != 3 and (k_scale != 1.0 or v_scale != 1.0):
+        raise ValueError(f"{name} only accepts non-unit cache scales for f8e4m3 caches, got cache={key_cache.dtype} k={k_scale} v={v_scale}")
+    if key_cache.dim() != 4 or value_cache.shape != key_cache.shape:
+        raise ValueError(f"{name} cache shape mismatch: {tuple(key_cache.shape)} and {tuple(value_cache.shape)}")
+    if not (key_cache.is_cuda and value_cache.is_cuda and key_cache.is_contiguous() and value_cache.is_contiguous()):
+        raise ValueError(f"{name}: the caches must be contiguous GPU tensors")
+    return code
+
+
+def reshape_and_cache_flashinfer(key: torch.Tensor, value: torch.Tensor, key_cache: torch.Tensor, value_cache: torch.Tensor, slot_mapping: torch.Tensor,
+                                 k_scale: float = 1.0, v_scale: float = 1.0) -> None:
+    """Scatter key / value [T, kv_heads, head_size] (row stride free) into the HND caches (backend/flashinfer.rs:71 `reshape_and_cache_flashinfer`):
+    token i goes to slot slot_mapping[i] = page * page_size + row (int64; negative slots are skipped).  An E4M3 cache stores value / scale."""
+    name = "reshape_and_cache_flashinfer"
+    if value.dtype != key.dtype:
+        raise ValueError(f"{name} expects matching K/V dtypes, got key={key.dtype}, value={value.dtype}")
+    code = _fi_cache(name, key.dtype, key_cache, value_cache, k_scale, v_scale)
+    if slot_mapping.dtype != torch.int64:
+        raise ValueError(f"{name} expects i64 slot_mapping")
+    if key.dim() != 3 or value.shape != key.shape:
+        raise ValueError(f"{name} key/value shape mismatch: {tuple(key.shape)} vs {tuple(value.shape)}")
+    num_tokens, num_heads, head_size = key.shape
+    for t in (key, value):
+        if not t.is_cuda or t.stride(2) != 1 or t.stride(1) != head_size:
+            raise ValueError(f"{name}: key / value must be GPU tensors, contiguous within a token")
+    _, cache_heads, block_size, cache_head_size = key_cache.shape
+    if cache_heads != num_heads or cache_head_size != head_size:
+        raise ValueError(f"{name} cache shape {tuple(key_cache.shape)} incompatible with key {tuple(key.shape)}")
+    if slot_mapping.dim() != 1 or slot_mapping.numel() != num_tokens or not slot_mapping.is_cuda:
+        raise ValueError(f"{name} slot_mapping length mismatch: expected {num_tokens}, got {tuple(slot_mapping.shape)}")
+    fn = _lib.sym("paged_attn", "reshape_and_cache_flashinfer", [_vp] * 5 + [_i] * 6 + [_f, _f, _u, _u, _vp])
+    fn(key.data_ptr(), value.data_ptr(), key_cache.data_ptr(), value_cache.data_ptr(), slot_mapping.contiguous().data_ptr(), num_tokens, num_heads,
+       head_size, block_size, key.stride(0), value.stride(0), k_scale, v_scale, _CODE[key.dtype], code, _stream())
+
+
+def gather_kv_cache_flashinfer(key_cache: torch.Tensor, value_cache: torch.Tensor, block_table: torch.Tensor, cu_seq_lens: torch.Tensor,
+                               out_dtype: torch.dtype, k_scale: float = 1.0, v_scale: float = 1.0):
+    """HND pages -> dense (K, V) [num_tokens, kv_heads, head_size] (backend/flashinfer.rs:550 `gather_kv_cache_flashinfer`); block_table int32
+    [seqs, max_blocks], cu_seq_lens int32 [seqs + 1] (its last entry is read back: it sizes the outputs).  E4M3 pages come back times the scale."""
+    name = "gather_kv_cache_flashinfer"
+    code = _fi_cache(name, out_dtype, key_cache, value_cache, k_scale, v_scale)
+    if block_table.dtype != torch.int32 or cu_seq_lens.dtype != torch.int32 or block_table.dim() != 2 or cu_seq_lens.dim() != 1:
+        raise ValueError(f"{name} expects i32 metadata: block_table [seqs, max_blocks], cu_seq_lens [seqs + 1]")
+    num_seqs = cu_seq_lens.numel() - 1
+    if block_table.shape[0] != num_seqs or not (block_table.is_cuda and cu_seq_lens.is_cuda):
+        raise ValueError(f"{name}: block_table {tuple(block_table.shape)} does not match cu_seq_lens {tuple(cu_seq_lens.shape)}")
+    block_table, cu_seq_lens = block_table.contiguous(), cu_seq_lens.contiguous()
+    _, kvh, block_size, head_size = key_cache.shape
+    num_tokens = int(cu_seq_lens[-1].item())
+    k_out = torch.empty(num_tokens, kvh, head_size, dtype=out_dtype, device=key_cache.device)
+    v_out = torch.empty_like(k_out)
+    if num_tokens:
+        fn = _lib.sym("paged_attn", "gather_kv_cache_flashinfer", [_vp] * 6 + [_i] * 6 + [_u, _u, _f, _f, _vp])
+        fn(key_cache.data_ptr(), value_cache.data_ptr(), k_out.data_ptr(), v_out.data_ptr(), block_table.data_ptr(), cu_seq_lens.data_ptr(), num_tokens,
+           num_seqs, block_size, block_table.stride(0), kvh, head_size, _CODE[out_dtype], code, k_scale, v_scale, _stream())
+    return k_out, v_out
+
+
+def flashinfer_decode_plan(context_lens, block_size: int, split_pages: int | None = None, padded_tiles_len: int | None = None,
+                           device=None) -> FlashInferDecodePlan:
+    """Host-side twin of `make_paged_kv_decode_tensors` (mistralrs-core/src/flashinfer/metadata.rs:150-216): request b gets
+    ceil(max(pages_b, 1) / split_pages) plan tiles (one with split_pages None), each split_pages * block_size keys (block_size with None, as there);
+    o_indptr counts them.  The lists are padded with zeros, mask 0, to padded_tiles_len (default: no padding, at least one entry) so that a captured
+    graph replays any plan of that size; more tiles than that is an error."""
+    chunk_pages = max(split_pages, 1) if split_pages is not None else None
+    req, tile, o_indptr = [], [], [0]
+    for b, n in enumerate(context_lens):
+        pages = max(-(-int(n) // block_size), 1)
+        chunks = 1 if chunk_pages is None else -(-pages // chunk_pages)
+        req += [b] * chunks
+        tile += list(range(chunks))
+        o_indptr.append(len(req))
+    valid = len(req)
+    if padded_tiles_len is None:
+        padded_tiles_len = max(valid, 1)
+    if valid > padded_tiles_len:
+        raise ValueError(f"paged kv decode tiles exceed padded length: tiles={valid} padded={padded_tiles_len}")
+    pad = [0] * (padded_tiles_len - valid)
+    i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=device)
+    return FlashInferDecodePlan(i32(req + pad), i32(tile + pad), i32(o_indptr), i32([(split_pages or 1) * block_size]),
+                                torch.tensor([1] * valid + pad, dtype=torch.uint8, device=device))
+
+
+def flashinfer_decode_split_pages(batch: int, num_kv_heads: int, max_kv_len: int, page_size: int) -> int:
+    """`split_pages` for `flashinfer_decode_plan` from host-known numbers.  The grid is (plan tiles, kv_heads) and a workgroup streams its keys with four
+    waves at one to three workgroups per compute unit, so the plan should offer about two workgroups per compute unit: chunks = 2 * 256 / (batch *
+    kv_heads).  A chunk is not made shorter than 256 keys: below that a wave has fewer than two 32-key tiles and nothing to overlap its loads with,
+    while the f32 partial a chunk writes (and the merge reads back) is, at G * head_size * 4 bytes against 256 * head_size * 4 bytes of bf16 K and V,
+    still under G / 256 of what the chunk reads.  One chunk (the return value covers max_kv_len) means the plan has one tile per request: the caller
+    may then pass partition=False and save the merge launch."""
+    pages = max(-(-max(max_kv_len, 1) // page_size), 1)
+    chunks = max(1, min(-(-2 * _FI_CUS // max(batch * num_kv_heads, 1)), pages * page_size // 256))
+    return -(-pages // chunks)
+
+
+def flashinfer_decode(q: torch.Tensor, key_cache: torch.Tensor, value_cache: torch.Tensor, paged_kv_indptr: torch.Tensor, paged_kv_indices: torch.Tensor,
+                      paged_kv_last_page_len: torch.Tensor, plan, sm_scale: float, *, window_left: int | None = None,
+                      logits_soft_cap: float | None = None, k_scale: float = 1.0, v_scale: float = 1.0, partition: bool = True) -> torch.Tensor:
+    """GQA decode over the HND paged cache (backend/flashinfer.rs:241 `flashinfer_decode`): q [batch, heads, head_size] (strides of the first two dims
+    free), f16 / bf16, caches of the same dtype or E4M3; request b owns pages paged_kv_indices[indptr[b] : indptr[b + 1]] with
+    paged_kv_last_page_len[b] keys in the last one; `plan` is the five tensors of `flashinfer_decode_plan` on the GPU -> [batch, heads, head_size];
+    a request without a visible key gets zeros.  window_left: key i is visible iff i + 1 + window_left >= kv_len; logits_soft_cap: s -> cap *
+    tanh(s / cap).  partition=False passes no scratch (tmp_v = NULL): the plan must then hold one tile per request (split_pages None).  Nothing is read
+    back from the device."""
+    name = "flashinfer_decode"
+    if q.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"{name}: only f16 / bf16 queries are supported, got {q.dtype}")
+    code = _fi_cache(name, q.dtype, key_cache, value_cache, k_scale, v_scale)
+    request_indices, kv_tile_indices, o_indptr, kv_chunk_size, block_valid_mask = plan
+    meta = dict(paged_kv_indptr=paged_kv_indptr, paged_kv_indices=paged_kv_indices, paged_kv_last_page_len=paged_kv_last_page_len,
+                request_indices=request_indices, kv_tile_indices=kv_tile_indices, o_indptr=o_indptr, kv_chunk_size=kv_chunk_size)
+    for what, t in meta.items():
+        if t.dtype != torch.int32:
+            raise ValueError(f"{name} expects {what} to be i32")
+    if block_valid_mask.dtype not in (torch.uint8, torch.bool):
+        raise ValueError(f"{name} expects block_valid_mask to be u8")
+    meta["block_valid_mask"] = block_valid_mask
+    if q.dim() != 3 or not q.is_cuda or q.stride(2) != 1:
+        raise ValueError(f"{name}: q must be a GPU tensor [batch, heads, head_size] with contiguous rows, got {tuple(q.shape)}")
+    batch, num_heads, head_size = q.shape
+    _, num_kv_heads, page_size, cache_head_size = key_cache.shape
+    if cache_head_size != head_size:
+        raise ValueError(f"{name} cache shape {tuple(key_cache.shape)} incompatible with query {tuple(q.shape)}")
+    if any(t.dim() != 1 or not t.is_cuda for t in meta.values()):
+        raise ValueError(f"{name}: the request lists and the plan must be GPU vectors")
+    padded = request_indices.numel()
+    if (paged_kv_indptr.numel() != batch + 1 or paged_kv_last_page_len.numel() != batch or padded < batch or kv_tile_indices.numel() != padded
+            or o_indptr.numel() != batch + 1 or kv_chunk_size.numel() != 1 or block_valid_mask.numel() != padded):
+        raise ValueError(f"{name} metadata shapes are invalid")
+    if num_kv_heads < 1 or num_heads % num_kv_heads:
+        raise ValueError(f"{name}: {num_heads} heads are not a multiple of {num_kv_heads} kv heads")
+    if head_size not in _FI_HEAD_SIZES or page_size not in (16, 32) or num_heads // num_kv_heads > 16:
+        raise ValueError(f"{name}: head_size must be 64 / 128 / 256, page size 16 / 32 and heads / kv_heads <= 16, got {head_size}, {page_size}, "
+                         f"{num_heads // num_kv_heads}")
+    if window_left is not None and window_left < 0:
+        raise ValueError(f"{name}: window_left must be >= 0 or None")
+    if logits_soft_cap is not None and not (math.isfinite(logits_soft_cap) and logits_soft_cap > 0.0):
+        raise ValueError(f"{name}: logits_soft_cap must be finite and positive, or None")
+    meta = {k: t.contiguous() for k, t in meta.items()}
+    out = torch.empty(batch, num_heads, head_size, dtype=q.dtype, device=q.device)
+    tmp_v = tmp_s = None
+    if partition:  # f32 partials [padded, heads, head_size] and their log-sum-exp [padded, heads]
+        v_bytes = padded * num_heads * head_size * 4
+        tmp_v = _workspace(q.device, v_bytes + padded * num_heads * 4).data_ptr()
+        tmp_s = tmp_v + v_bytes
+    fn = _lib.sym("paged_attn", "flashinfer_decode", [_vp] * 14 + [_i] * 8 + [_f, _i, _f, _f, _f, _u, _u, _vp], C.c_int32)
+    rc = fn(q.data_ptr(), key_cache.data_ptr(), value_cache.data_ptr(), meta["paged_kv_indptr"].data_ptr(), meta["paged_kv_indices"].data_ptr(),
+            meta["paged_kv_last_page_len"].data_ptr(), meta["request_indices"].data_ptr(), meta["kv_tile_indices"].data_ptr(),
+            meta["o_indptr"].data_ptr(), meta["kv_chunk_size"].data_ptr(), meta["block_valid_mask"].data_ptr(), out.data_ptr(), tmp_v, tmp_s, batch,
+            padded, num_heads, num_kv_heads, head_size, page_size, q.stride(0), q.stride(1), sm_scale, -1 if window_left is None else window_left,
+            0.0 if logits_soft_cap is None else logits_soft_cap, k_scale, v_scale, _CODE[q.dtype], code, _stream())
+    if rc != 0:
+        raise ValueError(f"{name}: flashinfer_decode returned {rc}")
     return out
 
 
